@@ -10,9 +10,16 @@ max over K, skip Conv1d 32->64, ReLU; loss = out.sum(); grads w.r.t. features an
 weights.  A "step" is one such pass over one batch of 32 synthetic clouds per GPU
 (distribution D1 of SURVEY.md section 8d: uniform cube -> centred -> unit sphere).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
          --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly K steps (one block) and prints the line.  --full
+adds everything else the line can carry: a short K is repeated as 25 fenced blocks (median
+reported), the index / MLP stream checks after the timed region, the per-kernel event passes and
+the roofline, the secondary figures (value_f32_dropin, the index-stage variants, value_no_syncbn,
+value_eager_collectives) and the CPU baseline.  --dump-outputs DIR writes what the timed path
+computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all).
 
 Multi-GPU: one process per GPU, batch sharded by cloud (weak scaling, 32 per
 GPU), SyncBatchNorm + gradient all-reduce over RCCL as the reference does at
@@ -242,6 +249,39 @@ def cpu_baseline(seconds_budget=14.0):
                       f"FPS/ball/group, torch-CPU for conv/BN/max"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all arrays together
+DUMP_MAX_ELEMENTS = 2 << 20      # an array larger than this is written as a fixed, seeded sample of its elements
+
+
+def snapshot(named):
+    """{name: tensor} -> {name: float32 / float64 host array}, copied now (later steps overwrite the device buffers)."""
+    out = {}
+    for name, t in named.items():
+        if t is None:
+            continue
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        out[name] = t.cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write every array as <path>/<name>.npy; one larger than DUMP_MAX_ELEMENTS becomes the elements at a sorted,
+    seeded sample of its flat positions (the same positions from run to run), and the total stays under the limit."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in sorted(arrays.items()):
+        a = np.ascontiguousarray(a)
+        if a.size > DUMP_MAX_ELEMENTS:
+            pick = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[pick]
+            name = name + "_sample"
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT_BYTES >> 20} MB of outputs")
+        np.save(os.path.join(path, name.replace(".", "_") + ".npy"), a)
+
+
 class Measured:
     pass
 
@@ -275,6 +315,7 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
     capture_collectives = distributed and args.graph_collectives != "off"
     eager_collectives = distributed and sync_bn and not capture_collectives
     params = [q for q in blk.parameters()]
+    param_names = [n for n, _ in blk.named_parameters()]
 
     # the two-stream pipeline pays only when the step is GPU-bound, i.e. under graph replay
     pipelined = fused_mlp and args.pipeline == "on"
@@ -335,6 +376,10 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
     cur_set = [0]
     ones = torch.ones(1, 1, 1, device=dev)
     graph_grads, last_grads = {}, [None]
+    # what the last step handed its caller (sampled centres, pooled features, the gradients): tensors of the eager step,
+    # or of a captured graph (refreshed in place by each replay)
+    last_run, graph_runs = [None], {}
+    record_outputs = bool(getattr(args, "dump_outputs", None))
 
     def clear_grads():
         for f in fs:
@@ -355,6 +400,10 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
                 torch.autograd.backward([out], [ones.expand_as(out)])
             else:
                 out.sum().backward()
+            if record_outputs:
+                # detached: a tensor kept with its grad_fn would keep this step's autograd graph alive into the capture
+                last_run[0] = {"new_xyz": new_p.detach(), "features": out.detach(), "grad_input_features": fs[i].grad,
+                               **{"grad_" + n: q.grad for n, q in zip(param_names, params)}}
 
     def index_steps(count, dst):
         if args.index_overlap == "on":
@@ -447,6 +496,7 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
                 mlp_graphs[cur] = g
                 # each capture owns its gradient tensors; a replay refreshes them in place
                 graph_grads[cur] = [q.grad for q in params if q.grad is not None]
+                graph_runs[cur] = last_run[0]
                 if pipelined:
                     index_graphs[cur], _, r.graph_nodes["index"] = graphs.capture(lambda: index_steps(spg, cur),
                                                                                   what="the index stages' graph")
@@ -456,6 +506,7 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
                 launch(spg, cur, lambda n, c: mlp_graphs[c].replay(),
                        (lambda n, d: None) if args.diag_freeze_index else (lambda n, d: index_graphs[d].replay()))
                 last_grads[0] = graph_grads[cur]
+                last_run[0] = graph_runs[cur]
                 if pipelined:
                     cur_set[0] ^= 1
         except Exception as exc:                      # capture is an optimisation, never a requirement
@@ -478,17 +529,20 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
     # (a replay of an spg-step graph counts as spg steps: exactly `steps` steps are timed)
     # (warm-up is rounded UP to whole replays: at least `warmup` untimed steps)
     r.elapsed = dp.timed_steps(step, steps // spg, -(-warmup // spg), dev)
-    # A short timed region (the driver's --steps 20 is ONE graph replay of 3 ms) is repeated: the same K-step block,
-    # fenced on both sides every time, `repeats` times; the MEDIAN block is reported, min / max beside it.
+    # --full: a short timed region (the driver's --steps 20 is ONE graph replay of 3 ms) is repeated: the same K-step
+    # block, fenced on both sides every time, `repeats` times; the MEDIAN block is reported, min / max beside it.
     r.blocks = [r.elapsed]
     if repeats > 1:
         for _ in range(repeats - 1):
             r.blocks.append(dp.timed_steps(step, steps // spg, 0, dev))
         r.elapsed = sorted(r.blocks)[len(r.blocks) // 2]
+    # the last timed step's results, copied before anything below launches another step
+    r.outputs = snapshot(last_run[0]) if record_outputs else None
     r.steps, r.spg, r.use_graph, r.pipelined, r.fused_mlp = steps, spg, use_graph, pipelined, fused_mlp
     r.index_batch = index_batch if pipelined and args.index_overlap != "on" else 1
     r.index_verified = None
-    if pipelined:
+    full = getattr(args, "full", True)
+    if pipelined and full:
         # The index stages ran BESIDE the MLP kernels all through the timed region (two graphs on two streams).  Their
         # inputs never change, so both sets must hold exactly what the same index stage yields on an idle device:
         # FPS picks, sampled coordinates, neighbours and occurrence counts, bit for bit.
@@ -526,7 +580,7 @@ def measure(args, dev, world, rank, local_rank, distributed, mlp, sync_bn, steps
         del ref
 
     r.mlp_verified = None
-    if pipelined and use_graph and fused_mlp and not distributed and r.index_verified is True:
+    if full and pipelined and use_graph and fused_mlp and not distributed and r.index_verified is True:
         # ... and the MLP kernels ran beside the index kernels: the parameter gradients the LAST replayed step left
         # against the same step launched eagerly on the idle device (same index set): BIT FOR BIT since round 5 (no float
         # atomics on the chain: the per-point sums are ordered sums of stored rows).
@@ -569,8 +623,13 @@ def workload_main(args, dev, world, rank, distributed):
         coll = workloads.collectives_per_step(job) if distributed else {}
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
+    eager_last = [None]
+
+    def recorded_step():
+        # detached: a kept grad_fn would hold this step's autograd graph alive into the capture below
+        eager_last[0] = {k: v.detach() if torch.is_tensor(v) else v for k, v in (job.step() or {}).items()}
     with torch.cuda.stream(side):
-        el_eager = dp.timed_steps(job.step, steps, warmup, dev)
+        el_eager = dp.timed_steps(recorded_step if args.dump_outputs else job.step, steps, warmup, dev)
     value_eager = B_PER_GPU * world * steps / el_eager
     launch, value, elapsed, nodes, last = "eager", value_eager, el_eager, None, None
     if args.graph != "off":
@@ -590,6 +649,12 @@ def workload_main(args, dev, world, rank, distributed):
             print(f"[bench] hipGraph capture of the {args.workload} step failed ({type(exc).__name__}: {exc}); "
                   "reporting the eager figure", file=sys.stderr, flush=True)
             torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        # the timed path's last step: what it returned (losses, generated clouds) and the parameters it left
+        ret = last if launch != "eager" else eager_last[0]
+        named = {k: v for k, v in (ret or {}).items() if torch.is_tensor(v) and v.is_floating_point()}
+        named.update({f"param_{net}.{n}": q for net, m in job.nets.items() for n, q in m.named_parameters()})
+        dump_outputs(args.dump_outputs, snapshot(named))
     names = {"classifier": "PointNeXt-S classifier training step (fwd + SmoothCE + bwd + clip + AdamW), BASELINE configs[2]",
              "gan": "AdaptPoint joint step: generator (Deformation + Mask controllers) + discriminator + feedback through the "
                     "eval-mode classifier, two Adam steps, BASELINE configs[3]",
@@ -636,11 +701,17 @@ def main():
     ap.add_argument("--points", type=int, default=1024, help="points per cloud of the training-step workloads")
     ap.add_argument("--overlap", choices=["on", "off"], default="on",
                     help="training-step workloads: the joint step as two lanes of one captured graph (GanStep(overlap=True))")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated timed blocks for a short --steps, the stream checks after the "
+                         "timed region, the per-kernel passes and roofline, the secondary figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed blocks of --steps steps each (median reported; 0 = auto: 25 when --steps < 400, else 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="timed blocks of --steps steps each (median reported; 0 = auto: with --full 25 when --steps < "
+                         "400, else 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary figures (value_f32_dropin at 1 GPU, value_no_syncbn at N>1)")
+                    help="--full without the secondary figures (value_f32_dropin at 1 GPU, value_no_syncbn at N>1)")
     ap.add_argument("--sync-bn", choices=["auto", "on", "off"], default="auto",
                     help="BatchNorm statistics at world_size>1.  auto = on: SyncBatchNorm, what the "
                          "reference forces (examples/classification/main.py:27): four small statistics "
@@ -723,13 +794,14 @@ def main():
         from adaptpoint_amd import set_abstraction as _sa_mod
         _sa_mod.PREFER_WIDE = True
     sync_bn = distributed and args.sync_bn != "off"          # auto = on, as the reference (main.py:27)
-    # fewer than ~400 steps are less than 0.1 s of work: repeat the K-step block and report the median (keeps `steps` = K)
-    repeats = args.repeats if args.repeats > 0 else (25 if args.steps < 400 else 1)
+    # --full: fewer than ~400 steps are less than 0.1 s of work: repeat the K-step block and report the median (keeps
+    # `steps` = K); a plain run times exactly one block of K steps
+    repeats = args.repeats if args.repeats > 0 else (25 if args.full and args.steps < 400 else 1)
     # N>1: the SAFE launch structure is measured FIRST (the step run eagerly around its collectives: nothing of RCCL
     # inside a hipGraph), the captured-collectives structure after it: a capture that fails falls back to the former,
     # and the line carries both figures.  (No multi-rank run of either exists: one-GPU boxes only.)
     value_eager_collectives = None
-    if distributed and sync_bn and args.graph_collectives != "off" and not args.no_secondary:
+    if args.full and distributed and sync_bn and args.graph_collectives != "off" and not args.no_secondary:
         import copy as _copy
         safe_args = _copy.copy(args)
         safe_args.graph_collectives = "off"
@@ -737,8 +809,105 @@ def main():
         ms = measure(safe_args, dev, world, rank, local_rank, distributed, args.mlp, sync_bn, sec, 4)
         value_eager_collectives = round(B_PER_GPU * world * sec / ms.elapsed, 2)
     m = measure(args, dev, world, rank, local_rank, distributed, args.mlp, sync_bn, args.steps, args.warmup, repeats)
-    elapsed, spg, use_graph, pipelined, fused_mlp, eager_step = (m.elapsed, m.spg, m.use_graph, m.pipelined,
-                                                                 m.fused_mlp, m.eager_step)
+    elapsed, spg, use_graph, pipelined, fused_mlp = m.elapsed, m.spg, m.use_graph, m.pipelined, m.fused_mlp
+    total_clouds = B_PER_GPU * world * args.steps
+    value = total_clouds / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m.outputs)
+    roofline = kernel_passes(args, m, world) if args.full else None
+
+    from adaptpoint_amd import set_abstraction as _sa
+    result = {
+        "metric": "set-abstraction fwd+bwd point-clouds/sec (B=32,N=1024)",
+        "value": round(value, 2), "unit": "point-clouds/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+        "timed_blocks": len(m.blocks),       # blocks of `steps` steps, each fenced on both sides; median reported
+        "ms_per_step_min": round(1e3 * min(m.blocks) / args.steps, 4),
+        "ms_per_step_max": round(1e3 * max(m.blocks) / args.steps, 4),
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if fused_mlp else "f32", "data": "synthetic",
+        "config": {"workload": ("DIAGNOSTIC (--diag-freeze-index: index stages NOT in the timed region; not the metric): "
+                                if args.diag_freeze_index else "")
+                               + "PointNeXt-S stage-1 SetAbstraction fwd+bwd, B=32/GPU N=1024 "
+                                 "npoint=512 nsample=32 r=0.15 C 32->64 (BASELINE configs[1])",
+                   "distribution": {"D1": "D1: uniform cube centred+scaled to the unit sphere",
+                                    "D2": "D2: unit-sphere surface + N(0,0.01) jitter"}[args.distribution],
+                   "seed": args.seed,
+                   "mlp": ({"fused-bf16x3": "fused bf16 MFMA on split hi+lo operands (3 MFMAs per product, "
+                                            "f32 accumulate; forward within 7e-5 of an fp32 chain), "
+                                            "f32 BatchNorm partial sums added exactly (integer accumulators) or in f64",
+                            "fused-bf16": "fused bf16 MFMA (operands rounded to bf16, f32 accumulate), "
+                                          "f32 BatchNorm partial sums added exactly (integer accumulators) or in f64",
+                            "torch-f32": "unfused: extension ops + PyTorch fp32 conv/BN"}[args.mlp]),
+                   "kernels": args.kernels,
+                   "tile_map": ("both passes over the index stage's distinct-hit tile map (ball-query fill copies "
+                                "folded into one row with a multiplicity: 3.7x fewer MFMA tiles); the backward pass stores its "
+                                "rows of g_u through the map's row map (point-sorted order) and the per-point kernel sums a "
+                                "point's consecutive rows in ascending order: no float atomics, gradients bit-reproducible"
+                                if (fused_mlp and args.kernels == "resident") else
+                                ("all passes over the distinct-hit tile map; per-point sums through its inverse map "
+                                 "(no float atomics: gradients bit-reproducible)" if fused_mlp else "none")),
+                   "launch": (f"hipGraph replay, {spg} step(s) per graph" if use_graph else "eager"),
+                   "graph_nodes": getattr(m, "graph_nodes", None),     # node census of the captured graphs (no memset nodes)
+                   "launches_per_step": ("3 forward + 4 backward on the MLP stream (BatchNorm folds and per-channel "
+                                         "constants are prologues of their consumer kernels)" if fused_mlp and args.kernels == "resident" else None),
+                   "pipeline": (f"index stages (FPS + ball query + occurrence statistics + tile map + row map) of the NEXT launch's batches on a second stream, "
+                                f"{m.index_batch} batch(es) per sampler launch, beside the MLP fwd+bwd of the "
+                                "current batch(es); the two streams meet once per launch" if pipelined else "none"),
+                   "global_batch": B_PER_GPU * world,
+                   "fused_fallbacks": sum(_sa.FUSED_FALLBACKS.values()),
+                   "deterministic_gradients": bool(fused_mlp),       # no float atomics on the fused chain (round 5)
+                   "parallelism": f"dp{world}" + ("+syncbn" if sync_bn else "")
+                                  + ("+flat-allreduce" if distributed else "")
+                                  + ("+collectives-in-graph" if getattr(m, "capture_collectives", False) else "")},
+        "roofline": roofline,
+    }
+    if value_eager_collectives is not None:
+        result["value_eager_collectives"] = value_eager_collectives
+    if args.full and not args.no_secondary:
+        sec_steps = max(4, min(args.steps, 40))
+        if distributed and sync_bn:
+            # the cheaper step the reference never runs: per-rank BatchNorm statistics, graph replay + one all-reduce
+            m2 = measure(args, dev, world, rank, local_rank, distributed, args.mlp, False, sec_steps, 4)
+            result["value_no_syncbn"] = round(B_PER_GPU * world * sec_steps / m2.elapsed, 2)
+        elif not distributed and fused_mlp:
+            # the bit-for-bit interoperable path: nine drop-in operators + PyTorch fp32 conv/BN (eager)
+            m2 = measure(args, dev, world, rank, local_rank, distributed, "torch-f32", False, sec_steps, 4)
+            result["value_f32_dropin"] = round(B_PER_GPU * sec_steps / m2.elapsed, 2)
+            if pipelined and args.index_batch == 0 and args.steps % 20 == 0:
+                # What the headline assumes, stated beside it: `value` runs the index stages (FPS + ball query) of 20 batches
+                # in ONE stacked launch on a second stream, a replay ahead of the MLP steps that consume them.  The same
+                # run batch by batch (one index launch per step, still a replay ahead), and with no second stream at all
+                # (index stage in line, in front of each step's MLP -- what a consumer of freshly GENERATED coordinates,
+                # e.g. the AdaptPoint feedback pass, gets):
+                import copy as _copy
+                v_steps = min(args.steps, 400)
+                a1 = _copy.copy(args)
+                a1.index_batch = 1
+                m4 = measure(a1, dev, world, rank, local_rank, distributed, args.mlp, False, v_steps, 40, repeats=5)
+                result["value_index_batch_1"] = round(B_PER_GPU * v_steps / m4.elapsed, 2)
+                result["index_batch_1_verified"] = m4.index_verified
+                a2 = _copy.copy(args)
+                a2.pipeline = "off"
+                m5 = measure(a2, dev, world, rank, local_rank, distributed, args.mlp, False, v_steps, 40, repeats=5)
+                result["value_no_pipeline"] = round(B_PER_GPU * v_steps / m5.elapsed, 2)
+            if args.mlp == "fused-bf16x3" and fused_mlp:
+                # bit-reproducible gradients are the only mode since round 5 (rounds 3-4: a separate, slower mode with 64-bit
+                # fixed-point atomics, reported here): the figure IS `value`
+                result["value_deterministic"] = result["value"]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline()
+    if distributed:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+
+
+def kernel_passes(args, m, world):
+    """--full: the per-kernel event passes after the timed region and the roofline of the dominant kernel."""
+    elapsed, spg, pipelined, fused_mlp, eager_step = m.elapsed, m.spg, m.pipelined, m.fused_mlp, m.eager_step
     # The timed step issues whole launch sequences (one C call per direction, or one hipGraph),
     # which cannot carry per-kernel events.  The dominant kernel is therefore timed right after
     # the timed region: the same launch, same inputs, same stream, HIP events around it.
@@ -764,8 +933,6 @@ def main():
     per_kernel_us = {k: v[0] for k, v in per_kernel_stats.items()}
     restore()
 
-    total_clouds = B_PER_GPU * world * args.steps
-    value = total_clouds / elapsed
     ab = algorithmic_bytes(B_PER_GPU, fused=fused_mlp)
     for k in ("fps", "ball_query", "sa_point_geo"):   # index launches cover index_batch batches
         ab[k] *= m.index_batch
@@ -875,94 +1042,7 @@ def main():
         "kernel_set_is_default": sorted(kernels) == sorted(DEFAULT_KERNELS),
         "traffic_file_covers_kernel_set": bool(traffic) and sorted(traffic) == sorted(kernels),
     })
-
-    from adaptpoint_amd import set_abstraction as _sa
-    result = {
-        "metric": "set-abstraction fwd+bwd point-clouds/sec (B=32,N=1024)",
-        "value": round(value, 2), "unit": "point-clouds/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-        "timed_blocks": len(m.blocks),       # blocks of `steps` steps, each fenced on both sides; median reported
-        "ms_per_step_min": round(1e3 * min(m.blocks) / args.steps, 4),
-        "ms_per_step_max": round(1e3 * max(m.blocks) / args.steps, 4),
-        "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16" if fused_mlp else "f32", "data": "synthetic",
-        "config": {"workload": ("DIAGNOSTIC (--diag-freeze-index: index stages NOT in the timed region; not the metric): "
-                                if args.diag_freeze_index else "")
-                               + "PointNeXt-S stage-1 SetAbstraction fwd+bwd, B=32/GPU N=1024 "
-                                 "npoint=512 nsample=32 r=0.15 C 32->64 (BASELINE configs[1])",
-                   "distribution": {"D1": "D1: uniform cube centred+scaled to the unit sphere",
-                                    "D2": "D2: unit-sphere surface + N(0,0.01) jitter"}[args.distribution],
-                   "seed": args.seed,
-                   "mlp": ({"fused-bf16x3": "fused bf16 MFMA on split hi+lo operands (3 MFMAs per product, "
-                                            "f32 accumulate; forward within 7e-5 of an fp32 chain), "
-                                            "f32 BatchNorm partial sums added exactly (integer accumulators) or in f64",
-                            "fused-bf16": "fused bf16 MFMA (operands rounded to bf16, f32 accumulate), "
-                                          "f32 BatchNorm partial sums added exactly (integer accumulators) or in f64",
-                            "torch-f32": "unfused: extension ops + PyTorch fp32 conv/BN"}[args.mlp]),
-                   "kernels": args.kernels,
-                   "tile_map": ("both passes over the index stage's distinct-hit tile map (ball-query fill copies "
-                                "folded into one row with a multiplicity: 3.7x fewer MFMA tiles); the backward pass stores its "
-                                "rows of g_u through the map's row map (point-sorted order) and the per-point kernel sums a "
-                                "point's consecutive rows in ascending order: no float atomics, gradients bit-reproducible"
-                                if (fused_mlp and args.kernels == "resident") else
-                                ("all passes over the distinct-hit tile map; per-point sums through its inverse map "
-                                 "(no float atomics: gradients bit-reproducible)" if fused_mlp else "none")),
-                   "launch": (f"hipGraph replay, {spg} step(s) per graph" if use_graph else "eager"),
-                   "graph_nodes": getattr(m, "graph_nodes", None),     # node census of the captured graphs (no memset nodes)
-                   "launches_per_step": ("3 forward + 4 backward on the MLP stream (BatchNorm folds and per-channel "
-                                         "constants are prologues of their consumer kernels)" if fused_mlp and args.kernels == "resident" else None),
-                   "pipeline": (f"index stages (FPS + ball query + occurrence statistics + tile map + row map) of the NEXT launch's batches on a second stream, "
-                                f"{m.index_batch} batch(es) per sampler launch, beside the MLP fwd+bwd of the "
-                                "current batch(es); the two streams meet once per launch" if pipelined else "none"),
-                   "global_batch": B_PER_GPU * world,
-                   "fused_fallbacks": sum(_sa.FUSED_FALLBACKS.values()),
-                   "deterministic_gradients": bool(fused_mlp),       # no float atomics on the fused chain (round 5)
-                   "parallelism": f"dp{world}" + ("+syncbn" if sync_bn else "")
-                                  + ("+flat-allreduce" if distributed else "")
-                                  + ("+collectives-in-graph" if getattr(m, "capture_collectives", False) else "")},
-        "roofline": roofline,
-    }
-    if value_eager_collectives is not None:
-        result["value_eager_collectives"] = value_eager_collectives
-    if not args.no_secondary:
-        sec_steps = max(4, min(args.steps, 40))
-        if distributed and sync_bn:
-            # the cheaper step the reference never runs: per-rank BatchNorm statistics, graph replay + one all-reduce
-            m2 = measure(args, dev, world, rank, local_rank, distributed, args.mlp, False, sec_steps, 4)
-            result["value_no_syncbn"] = round(B_PER_GPU * world * sec_steps / m2.elapsed, 2)
-        elif not distributed and fused_mlp:
-            # the bit-for-bit interoperable path: nine drop-in operators + PyTorch fp32 conv/BN (eager)
-            m2 = measure(args, dev, world, rank, local_rank, distributed, "torch-f32", False, sec_steps, 4)
-            result["value_f32_dropin"] = round(B_PER_GPU * sec_steps / m2.elapsed, 2)
-            if pipelined and args.index_batch == 0 and args.steps % 20 == 0:
-                # What the headline assumes, stated beside it: `value` runs the index stages (FPS + ball query) of 20 batches
-                # in ONE stacked launch on a second stream, a replay ahead of the MLP steps that consume them.  The same
-                # run batch by batch (one index launch per step, still a replay ahead), and with no second stream at all
-                # (index stage in line, in front of each step's MLP -- what a consumer of freshly GENERATED coordinates,
-                # e.g. the AdaptPoint feedback pass, gets):
-                import copy as _copy
-                v_steps = min(args.steps, 400)
-                a1 = _copy.copy(args)
-                a1.index_batch = 1
-                m4 = measure(a1, dev, world, rank, local_rank, distributed, args.mlp, False, v_steps, 40, repeats=5)
-                result["value_index_batch_1"] = round(B_PER_GPU * v_steps / m4.elapsed, 2)
-                result["index_batch_1_verified"] = m4.index_verified
-                a2 = _copy.copy(args)
-                a2.pipeline = "off"
-                m5 = measure(a2, dev, world, rank, local_rank, distributed, args.mlp, False, v_steps, 40, repeats=5)
-                result["value_no_pipeline"] = round(B_PER_GPU * v_steps / m5.elapsed, 2)
-            if args.mlp == "fused-bf16x3" and fused_mlp:
-                # bit-reproducible gradients are the only mode since round 5 (rounds 3-4: a separate, slower mode with 64-bit
-                # fixed-point atomics, reported here): the figure IS `value`
-                result["value_deterministic"] = result["value"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline()
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result), flush=True)
+    return roofline
 
 
 if __name__ == "__main__":

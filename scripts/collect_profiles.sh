@@ -9,11 +9,11 @@ O=$R/gpurun_out/$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 what=${1:-bench}
-B="--no-cpu-baseline --no-secondary"
+B="--full --no-cpu-baseline --no-secondary"
 
 if [ "$what" = bench ]; then
-    python $R/bench.py > $O/${T}_bench_default.json 2> $O/bench_default.err
-    python $R/bench.py --steps 20 --warmup 5 > $O/${T}_bench_driver_flags.json 2>> $O/bench_default.err
+    python $R/bench.py --full > $O/${T}_bench_default.json 2> $O/bench_default.err
+    python $R/bench.py --full --steps 20 --warmup 5 > $O/${T}_bench_driver_flags.json 2>> $O/bench_default.err
     rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o b -- python $R/bench.py --steps 2000 --warmup 200 $B > $O/prof_bench.log 2>&1
     cp $O/prof_bench/b_kernel_stats.csv $O/${T}_bench_default_kernel_stats.csv
     python $R/scripts/steady_stats.py $O/prof_bench/b_kernel_trace.csv sa_prep_stats 20 3 --csv $O/${T}_bench_default_steady_per_replay.csv > $O/${T}_bench_default_steady.txt
@@ -28,7 +28,7 @@ if [ "$what" = bench ]; then
     : > $O/${T}_bench_nccl_world1.jsonl
     for f in "" "--sync-bn off"; do
         APN_BENCH_FORCE_DISTRIBUTED=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29741 \
-            python $R/bench.py --gpus 1 --no-cpu-baseline $f 2>/dev/null | grep '^{' >> $O/${T}_bench_nccl_world1.jsonl
+            python $R/bench.py --gpus 1 --full --no-cpu-baseline $f 2>/dev/null | grep '^{' >> $O/${T}_bench_nccl_world1.jsonl
     done
     python $R/scripts/stamp_passes.py > $O/${T}_pass_stamps.txt 2>/dev/null
 fi

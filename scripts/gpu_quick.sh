@@ -15,7 +15,7 @@ if [ "$tests" != "-" ]; then
     tail -4 $O/${tag}_tests.log
     if [ $rc -ne 0 ]; then grep -n "Error\|assert\|FAILED" $O/${tag}_tests.log | head -20; exit $rc; fi
 fi
-python bench.py --no-cpu-baseline --no-secondary "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -20 $O/${tag}_bench.err; exit 1; }
+python bench.py --full --no-cpu-baseline --no-secondary "$@" > $O/${tag}_bench.json 2> $O/${tag}_bench.err || { tail -20 $O/${tag}_bench.err; exit 1; }
 python - "$O/${tag}_bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

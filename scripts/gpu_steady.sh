@@ -7,7 +7,7 @@ mkdir -p $O
 tag=${1:-s}
 shift
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o b -- python $R/bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-secondary "$@" > $O/${tag}_prof.log 2>&1 || { tail -20 $O/${tag}_prof.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o b -- python $R/bench.py --steps 2000 --warmup 200 --full --no-cpu-baseline --no-secondary "$@" > $O/${tag}_prof.log 2>&1 || { tail -20 $O/${tag}_prof.log; exit 1; }
 python $R/scripts/steady_stats.py $O/prof_$tag/b_kernel_trace.csv sa_prep_stats 20 3 > $O/${tag}_steady.txt
 cp $O/prof_$tag/b_kernel_stats.csv $O/${tag}_kernel_stats.csv
 rm -rf $O/prof_$tag

@@ -25,13 +25,15 @@ observable here), else the seed is rejected.
 Fixtures store OUTPUTS (and small state_dicts); inputs are regenerated from
 seeds by tests/golden_inputs.py.
 
-    python tests/golden/make_golden.py [all | pointnet2 | adaptpoint | pins | classifier]
+    python tests/golden/make_golden.py [all | pointnet2 | adaptpoint | pins | classifier | integrate]
 
 `pointnet2` writes pointnet2_golden.npz (G1-G8: operators, SetAbstraction, the PointNeXt-S
 classifier, the imitator's grouper / attention / predictor network); `adaptpoint` writes
 adaptpoint_golden.npz (G9-G13: the generator with pinned random draws, the discriminator, one
 `train_gan` iteration and one `train_one_epoch` iteration replayed statement for statement over
-the reference's modules, three_interpolation and KNNGroup).
+the reference's modules, three_interpolation and KNNGroup); `integrate` writes
+integrate_reference_golden.npz (G19: the classes `adaptpoint_amd.integrate` patches, run by their
+own forwards, for tests/test_integrate_reference_cpu.py).
 """
 import os
 import sys
@@ -890,8 +892,95 @@ def main_pins():
     print("wrote", path, os.path.getsize(path) // 1024, "KiB,", len(out), "arrays")
 
 
+def integrate_modules(ref_pointnext, ref_gen, EasyDict):
+    """The six modules tests/test_integrate_reference_cpu.py patches, constructed in its order after
+    torch.manual_seed(0): name -> module (the classes are the reference's here, the test's stand-ins there)."""
+    torch.manual_seed(0)
+    sa = ref_pointnext.SetAbstraction(
+        32, 64, layers=2, stride=2,
+        group_args=EasyDict(NAME='ballquery', radius=0.15, nsample=32, normalize_dp=True),
+        norm_args={'norm': 'bn'}, act_args={'act': 'relu'}, conv_args={'order': 'conv-norm-act'},
+        sampler='fps', feature_type='dp_fj', use_res=True).train()
+    head = ref_pointnext.SetAbstraction(4, 32, layers=1, stride=1, group_args=EasyDict(NAME='ballquery', radius=0.15, nsample=32),
+                                        norm_args={'norm': 'bn'}, act_args={'act': 'relu'}, conv_args={'order': 'conv-norm-act'},
+                                        is_head=True).train()
+    odd = ref_pointnext.SetAbstraction(32, 64, layers=2, stride=2,
+                                       group_args=EasyDict(NAME='ballquery', radius=0.15, nsample=16, normalize_dp=True),
+                                       norm_args={'norm': 'bn'}, act_args={'act': 'relu'}, conv_args={'order': 'conv-norm-act'},
+                                       sampler='fps', feature_type='dp_df', use_res=True).train()
+    grp = ref_gen.PointsetGrouper(channel=16, reduce=2, kneighbors=24, radi=0.2)
+    with torch.no_grad():
+        grp.affine_alpha.uniform_(0.5, 1.5)
+        grp.affine_beta.uniform_(-0.2, 0.2)
+    att = ref_gen.Anchor_selfattention(32, 2).train()
+    cbr = ref_gen.ConvBNReLU1D(16, 32, bias=False).train()
+    return {"sa": sa, "head": head, "odd": odd, "grp": grp, "att": att, "cbr": cbr}
+
+
+def integrate_inputs():
+    p = _t(GI.unit_sphere_cloud(2, 256, seed=3))
+    f = _t(GI.seeded_normal((2, 32, 256), seed=4)).requires_grad_(True)
+    x4 = _t(GI.seeded_normal((2, 4, 256), seed=5))
+    pts = _t(GI.seeded_normal((2, 256, 16), seed=6)).requires_grad_(True)
+    xa = _t(GI.seeded_normal((2, 64, 32), seed=7))
+    xc = _t(GI.seeded_normal((2, 16, 256), seed=8))
+    return p, f, x4, pts, xa, xc
+
+
+def integrate_run_all(mods, inputs):
+    """One pass of every module: name -> [outputs and gradients] (the list order the test compares in)."""
+    p, f, x4, pts, xa, xc = inputs
+    sa, head, odd, grp, att, cbr = (mods[k] for k in ("sa", "head", "odd", "grp", "att", "cbr"))
+    out = {}
+    f1 = f.detach().clone().requires_grad_(True)
+    new_p, o = sa([p, f1])
+    (o * o).sum().backward()
+    out["sa"] = [new_p, o.detach(), f1.grad] + [q.grad.clone() for q in sa.parameters()]
+    sa.zero_grad()
+    out["head"] = [head([p, x4])[1].detach()]
+    out["odd"] = [odd([p, f.detach()])[1].detach()]
+    pt1 = pts.detach().clone().requires_grad_(True)
+    nx, g = grp(p, pt1)
+    g.square().sum().backward()
+    out["grp"] = [nx, g.detach(), pt1.grad, grp.affine_alpha.grad.clone()]
+    grp.zero_grad()
+    out["att"] = [att(xa, p[:, :64]).detach()]
+    out["cbr"] = [cbr(xc).detach()]
+    return out
+
+
+def main_integrate():
+    """G19: the four classes `adaptpoint_amd.integrate.patch_openpoints()` rebinds, run by their own (the reference's)
+    forwards over the oracle operators: every module's initial state_dict, its outputs and gradients, and its state_dict
+    after the pass (BatchNorm running statistics) -> integrate_reference_golden.npz."""
+    _, ref_pointnext, _ = import_reference()
+    from easydict import EasyDict
+    import openpoints.models_adaptpoint.generator_component4_15 as ref_gen
+    ref_gen.furthest_point_sample = _OracleOps.furthest_point_sample
+    ref_gen.ball_query = _OracleOps.ball_query
+    mods = integrate_modules(ref_pointnext, ref_gen, EasyDict)
+    out = {}
+    for k, m in mods.items():
+        out[f"{k}_keys"] = np.array(list(m.state_dict().keys()))
+        for name, v in m.state_dict().items():
+            out[f"{k}_init.{name}"] = v.detach().numpy().copy()
+    want = integrate_run_all(mods, integrate_inputs())
+    for k, vals in want.items():
+        for i, v in enumerate(vals):
+            out[f"{k}_out{i}"] = v.detach().numpy()
+        out[f"{k}_nout"] = np.array(len(vals))
+    for k, m in mods.items():
+        for name, v in m.state_dict().items():
+            out[f"{k}_after.{name}"] = v.detach().numpy().copy()
+    path = os.path.join(HERE, "integrate_reference_golden.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB,", len(out), "arrays")
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if what in ("all", "integrate"):
+        main_integrate()
     if what in ("all", "pointnet2"):
         main()
     if what in ("all", "adaptpoint"):

@@ -15,7 +15,7 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
 
 def _bench(extra):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary"] + extra, env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary"] + extra, env=env,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -66,8 +66,40 @@ def test_index_stage_beside_the_mlp_stream_is_bit_exact_at_full_length(dev):
     assert ix["verified_after_timed_region"] is True
     assert ix["mlp_stream_verified_after_timed_region"]["max_gradient_deviation_rel"] < 1e-5
     env = dict(os.environ, APN_FPS_RECORDS="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-secondary", "--steps", "200",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-secondary", "--steps", "200",
                           "--warmup", "20"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert line["roofline"]["index_stream"]["verified_after_timed_region"] is True
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_step(dev, tmp_path):
+    """A plain run: one timed block of exactly --steps steps, the headline keys and nothing of --full; --dump-outputs
+    writes the last timed step's results (float32 / float64, at most 64 MB), the same from run to run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    lines = []
+    for tag in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / tag)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        lines.append(json.loads(js[0]))
+    d = lines[0]
+    assert KEYS <= set(d) and d["steps"] == 8 and d["warmup"] == 2 and d["timed_blocks"] == 1
+    assert d["dtype"] == "bf16" and d["higher_is_better"] is True and d["config"]["launch"] == "hipGraph replay, 4 step(s) per graph"
+    assert abs(d["ms_per_step"] - 1e3 * 32 / d["value"]) <= 1e-3 * d["ms_per_step"] + 1e-4
+    assert d["roofline"] is None and "cpu_baseline" not in d and "value_f32_dropin" not in d
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"new_xyz.npy", "features.npy", "grad_input_features.npy", "grad_convs_0_0_weight.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "features.npy").shape == (32, 64, 512)
+    assert np.load(tmp_path / "a" / "grad_input_features.npy").shape == (32, 32, 1024)

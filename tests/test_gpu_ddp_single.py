@@ -17,7 +17,7 @@ def _run(extra, port):
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(port), APN_BENCH_FORCE_DISTRIBUTED="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10",
-                          "--warmup", "3", "--no-cpu-baseline"] + extra, env=env, capture_output=True,
+                          "--warmup", "3", "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
