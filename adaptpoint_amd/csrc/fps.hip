@@ -688,8 +688,7 @@ extern "C" int apn_furthest_point_sampling_tuned(int b, int n, int m, const floa
 extern "C" int apn_furthest_point_sampling_xyz(int b, int n, int m, const float *xyz, float *temp,
                                                int *idxs, float *new_xyz, void *stream) {
     if (n > 16384 || !new_xyz) return APN_EINVAL;
-    static const int env_waves = [] { const char *e = getenv("APN_FPS_WAVES"); return e ? atoi(e) : 0; }();
-    return fps_impl(b, n, m, xyz, temp, idxs, new_xyz, env_waves, fps_default_algo(), stream);
+    return fps_impl(b, n, m, xyz, temp, idxs, new_xyz, 0, fps_default_algo(), stream);
 }
 
 namespace apn {

@@ -26,8 +26,6 @@ statistics `Sampling.geo`), all on the current stream with no host reads, so a s
 With sync_bn=True the per-channel float64 sums are all-reduced across ranks
 (SyncBatchNorm semantics) at the four points where statistics leave the kernels.
 """
-import os
-
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -40,9 +38,7 @@ C_IN, C_MID, C_OUT, K_NS = 32, 32, 64, 32
 # tiles at stage 1.  The BACKWARD pass runs over it always (round 5): it stores the rows of g_u through the map's row map
 # (fused_wide.row_maps: a row's place in the point-sorted order) and the per-point kernel sums a point's consecutive rows
 # in ascending order -- no float atomics anywhere in the chain.  A caller that hands no index stage in gets both maps
-# built in line (two + one launches).
-# build the tile map in line for the FORWARD too when the caller hands no index stage in (training: forward + backward)
-TILE_MAP_INLINE = os.environ.get("APN_TMAP_INLINE", "1") == "1"
+# built in line (two + one launches) when a backward follows.
 # Bit-reproducible gradients are the ONLY mode since round 5 (every cross-workgroup sum is an integer accumulator set, a
 # fixed-order fold of partial rows, or the ordered sum of a point's rows); rounds 3-4 had a separate, slower mode
 # (64-bit fixed-point integer atomics for the per-point sums) behind this flag, which is kept as an accepted no-op.
@@ -61,20 +57,23 @@ _PREC = {"bf16": 1, "bf16x3": 2}
 PER_KERNEL_LAUNCH = False
 
 
+def covers(B, N, M, K, C, w1, w2, biased=False, momenta=()):
+    """Whether the fused kernels cover a block, on plain values: B clouds of N points, M queries of K neighbours, C input
+    channels, w1 / w2 the (out, in) channels of conv1 / conv2, biased: either conv has a bias, momenta: the BatchNorms'.
+    The 32 -> 32 -> 64, K = 32 shape, no more queries than support points (the backward walks query tiles alongside
+    point tiles), a batch that fits one grid dimension, and BatchNorms with a fixed momentum (the cumulative-average
+    mode `momentum=None` stays on the unfused path)."""
+    return (C == C_IN and K == K_NS and tuple(w1) == (C_MID, C_IN + 3) and tuple(w2) == (C_OUT, C_MID) and not biased
+            and (M is None or M <= N) and B <= 65535 and all(m is not None for m in momenta))
+
+
 def supported(p, f, idx_or_k, conv1, conv2, bns=(), npoint=None):
-    """Whether the fused kernels cover this block: the 32 -> 32 -> 64, K = 32 shape, float32 CUDA
-    tensors, no more queries than support points (the backward walks query tiles alongside point
-    tiles), a batch that fits one grid dimension, and BatchNorms with a fixed momentum (the
-    cumulative-average mode `momentum=None` stays on the unfused path)."""
+    """`covers` for float32 CUDA tensors and the modules themselves."""
     k = idx_or_k.shape[2] if torch.is_tensor(idx_or_k) else int(idx_or_k)
     m = idx_or_k.shape[1] if torch.is_tensor(idx_or_k) else npoint
     return (f.is_cuda and f.dtype == torch.float32 and p.dtype == torch.float32
-            and f.shape[1] == C_IN and k == K_NS
-            and tuple(conv1.weight.shape[:2]) == (C_MID, C_IN + 3)
-            and tuple(conv2.weight.shape[:2]) == (C_OUT, C_MID)
-            and conv1.bias is None and conv2.bias is None
-            and (m is None or m <= p.shape[1]) and p.shape[0] <= 65535
-            and all(bn.momentum is not None for bn in bns))
+            and covers(p.shape[0], p.shape[1], m, k, f.shape[1], conv1.weight.shape[:2], conv2.weight.shape[:2],
+                       conv1.bias is not None or conv2.bias is not None, [bn.momentum for bn in bns]))
 
 
 _FN = {}
@@ -480,20 +479,16 @@ class Sampling:
 
     def clouds(self, lo, hi):
         """The index stage of clouds lo..hi-1 as a `Sampling`-like view (no copy): index stages of
-        several batches computed in ONE launch over the stacked clouds are handed out per batch."""
+        several batches computed in ONE launch over the stacked clouds are handed out per batch.
+        The per-cloud tensors are sliced; everything else (the buffer, maps built over all clouds, the event) is None."""
         v = object.__new__(Sampling)
+        for name, t in vars(self).items():
+            setattr(v, name, t[lo:hi] if name in _PER_CLOUD and t is not None else None)
         v.shape = (hi - lo,) + self.shape[1:]
-        v.buf = None
-        v.fidx, v.new_p, v.idx = self.fidx[lo:hi], self.new_p[lo:hi], self.idx[lo:hi]
-        v.index = None
-        v.tmap = None
-        v.rowmap = None
-        v.geo = v.dd = None
-        v.ready = None
-        v.ties = None if self.ties is None else self.ties[lo:hi]
-        if self.geo is not None:
-            v.geo, v.dd = self.geo[lo:hi], self.dd[lo:hi]
         return v
+
+
+_PER_CLOUD = ("fidx", "new_p", "idx", "geo", "dd", "ties")
 
 
 @torch.no_grad()
@@ -598,19 +593,14 @@ class _SetAbstraction(torch.autograd.Function):
         p = p.contiguous()
         f = f.contiguous()
         smp = sampling if sampling is not None else sample_and_query(p, npoint, radius, geo=True)
-        if sampling is None and TILE_MAP_INLINE and any(ctx.needs_input_grad):
-            # the distinct-hit tile map, built in line (two launches): both passes then walk ~1/4 of the tiles -- forward
-            # 29 -> 20 us, backward 66 -> 34 us at B = 32, N = 1024
-            from . import fused_wide
-            smp.tmap = fused_wide.tile_map(smp.idx)
-            smp.rowmap = fused_wide.row_map(smp.tmap, p.shape[0], p.shape[1], npoint, fidx=smp.fidx)
         fidx, new_p, idx = smp.fidx, smp.new_p, smp.idx
         if p.requires_grad:
             new_p = new_p.clone()          # returned as a differentiable output
+        # (no index stage handed in: a training forward builds the tile map and its row map itself, both passes then
+        # walk ~1/4 of the tiles -- forward 29 -> 20 us, backward 66 -> 34 us at B = 32, N = 1024)
         fw = _Forward(p, f, new_p, idx, fidx, radius, conv1, bn1, conv2, bn2, skip_conv, relu,
-                      sync_bn, tmap=getattr(smp, "tmap", None), geo=getattr(smp, "geo", None),
-                      dd=getattr(smp, "dd", None), want_backward=any(ctx.needs_input_grad),
-                      rowmap=getattr(smp, "rowmap", None))
+                      sync_bn, tmap=smp.tmap, geo=smp.geo, dd=smp.dd, want_backward=any(ctx.needs_input_grad),
+                      rowmap=smp.rowmap)
         ctx.fw = fw
         ctx.save_for_backward(p, f)        # autograd's in-place version checks cover the inputs
         ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as zeros

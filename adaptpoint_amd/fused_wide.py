@@ -30,18 +30,25 @@ LEAN_MAX = 64        # widest C_in / C_mid whose dense products run in csrc/sa_w
 WIDTHS = (32, 64, 128, 256)
 
 
+def covers(B, M, K, C, w1, w2, biased=False, momenta=()):
+    """Whether these kernels cover a block, on plain values: B clouds, M queries of K neighbours, C input channels,
+    w1 / w2 the (out, in) channels of conv1 / conv2, biased: either conv has a bias, momenta: the BatchNorms'.
+    The kernels pack query ids into 24 bits (B * M is bounded)."""
+    H, O = w1[0], w2[0]
+    return (K == K_NS and H in WIDTHS and O == 2 * H and w1[1] == C + 3 and w2[1] == H and not biased
+            and B * M < 2 ** 24
+            and (64 * (H + 1) + (C + 3) * 65) * 4 <= 160 * 1024        # LDS of the per-point gradient kernel
+            and all(m is not None for m in momenta))
+
+
 def supported(p, f, idx_or_k, conv1, conv2, bns=(), npoint=None):
-    """npoint: the number of queries when `idx_or_k` is the neighbourhood size alone (the kernels pack query ids
-    into 24 bits: B * npoint is bounded)."""
+    """`covers` for float32 CUDA tensors and the modules themselves.  npoint: the number of queries when `idx_or_k` is
+    the neighbourhood size alone (default: one per point)."""
     k = idx_or_k.shape[2] if torch.is_tensor(idx_or_k) else int(idx_or_k)
     m = idx_or_k.shape[1] if torch.is_tensor(idx_or_k) else (p.shape[1] if npoint is None else int(npoint))
-    H, O = conv1.weight.shape[0], conv2.weight.shape[0]
-    return (f.is_cuda and f.dtype == torch.float32 and p.dtype == torch.float32 and k == K_NS
-            and H in WIDTHS and O == 2 * H and conv1.weight.shape[1] == f.shape[1] + 3
-            and conv2.weight.shape[1] == H and conv1.bias is None and conv2.bias is None
-            and p.shape[0] * m < 2 ** 24
-            and (64 * (H + 1) + (f.shape[1] + 3) * 65) * 4 <= 160 * 1024        # LDS of the per-point gradient kernel
-            and all(bn.momentum is not None for bn in bns))
+    return (f.is_cuda and f.dtype == torch.float32 and p.dtype == torch.float32
+            and covers(p.shape[0], m, k, f.shape[1], conv1.weight.shape[:2], conv2.weight.shape[:2],
+                       conv1.bias is not None or conv2.bias is not None, [bn.momentum for bn in bns]))
 
 
 def mfma_b_image(Bm, ct):

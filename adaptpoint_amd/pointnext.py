@@ -61,7 +61,6 @@ class PointNextEncoderS(nn.Module):
         Returns one `adaptpoint_amd.fused.Sampling` (or None) per block; `out`: buffers to fill.  events: record an
         event behind every block's index stage (`Sampling.ready`); `forward_cls_feat` then waits block by block, so
         a pyramid running on a side stream is consumed level by level instead of as a whole."""
-        from . import fused
         res, p = [], p0.contiguous()
         ties = None          # block k + 1 samples from block k's samples: the nested sampler (csrc/fps.hip, NEST)
         for i, stage in enumerate(self.encoder):
@@ -69,10 +68,9 @@ class PointNextEncoderS(nn.Module):
             if sa.is_head or sa.all_aggr:
                 res.append(None)
                 continue
-            smp = fused.sample_and_query(p, p.shape[1] // sa.stride, sa.grouper.radius, sa.grouper.nsample,
-                                         out=None if out is None else out[i], geo=sa._resident(), nested=True, ties=ties)
+            smp = sa.sample(p, out=None if out is None else out[i], nested=True, ties=ties)
             ties = smp.ties
-            # tile map + inverse map of the neighbourhoods, for the blocks on the width-generic kernels
+            # what the block's kernels derive from the neighbourhoods (tile map, row map or NeighbourIndex)
             sa.index_for(smp, p.shape[1], sa.convs[0][0].in_channels - 3, out=smp.index)
             if events:
                 from . import graphs
@@ -107,7 +105,7 @@ class PointNextEncoderS(nn.Module):
             pyramid = self.index_pyramid(p0.detach())
         for i, stage in enumerate(self.encoder):
             smp = None if pyramid is None else pyramid[i]
-            if smp is not None and getattr(smp, 'ready', None) is not None:
+            if smp is not None and smp.ready is not None:
                 torch.cuda.current_stream(p0.device).wait_event(smp.ready)
             p0, f0 = stage[0]([p0, f0], sampling=smp) if smp is not None else stage[0]([p0, f0])
         return f0.squeeze(-1)

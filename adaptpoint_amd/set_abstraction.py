@@ -9,11 +9,12 @@ pooling, optional residual.  Sub-module names and nesting match the reference
 state_dict loads unchanged.
 """
 import logging
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
 
-from . import layers, pointwise
+from . import fused, fused_wide, layers, pointwise
 from .layers import BallGrouper, make_grouper
 
 _log = logging.getLogger("adaptpoint_amd")
@@ -26,12 +27,70 @@ FUSED_FALLBACKS = {}
 # True: the width-generic kernels (csrc/sa_wide.hip) also take the 32 -> 32 -> 64 shape that the
 # register-resident kernels of csrc/sa_fused.hip specialise in (A/B switch for benchmarks and tests).
 PREFER_WIDE = False
-MAX_SAMPLE_SEQ_POINTS = 16384   # apn_sa_sample_seq / apn_furthest_point_sampling_xyz: clouds kept in registers / LDS
-COMPACT_RESIDENT = True      # the register-resident kernels run over the distinct-hit tile map when a Sampling carries one
+# the fused index stage (apn_sa_sample_seq -> the resident samplers of csrc/fps.hip) keeps a cloud in registers / LDS:
+# larger clouds take the unfused operators, whose FPS is the streaming sampler (csrc/fps.hip: fps_stream_kernel)
+MAX_SAMPLE_SEQ_POINTS = 16384
+
+# The paths of one call (`route`)
+STEM = "stem"                # is_head: the 1x1 convolutions alone (csrc/pointwise.hip when fused)
+GROUP_ALL = "group_all"      # all_aggr, fused: the per-point contraction kernels, then the pool
+RESIDENT = "resident"        # the whole block on the register-resident kernels (fused.fused_set_abstraction)
+WIDE = "wide"                # the block after its index stage on the width-generic kernels (fused_wide.block)
+GROUPED = "grouped"          # unfused index stage, then the grouped MLP alone (fused / fused_wide.grouped_mlp_max)
+COMPOSED = "composed"        # the unfused operators + PyTorch
 
 
-def fused_wide_first():
-    return PREFER_WIDE
+class Plan(NamedTuple):
+    """A block's structure as the kernels see it, from its modules alone (`SetAbstraction.plan`)."""
+    kind: str                # "stem", "group_all" or "ball" (FPS + neighbourhoods)
+    fused: bool
+    mlp: tuple               # (conv1, bn1, conv2, bn2) when the MLP has the fused kernels' structure, else None
+    relu_after: bool         # a ReLU after the last BatchNorm
+    res: bool                # a residual branch (use_res)
+    skip: nn.Module          # its 1x1 Conv1d (None: no branch, or one the kernels cannot take)
+    stride: int
+    K: int                   # neighbours per query
+    widths: tuple            # the convolutions' output channels
+    w1: tuple = None         # (out, in) channels of conv1 and of conv2; biased: either has a bias
+    w2: tuple = None
+    biased: bool = False
+
+
+class Route(NamedTuple):
+    """Where ONE call of a block runs (`route`)."""
+    path: str
+    wide: bool = False       # on the width-generic kernels (WIDE; GROUPED through fused_wide.grouped_mlp_max)
+    fuse_skip: bool = False  # the residual branch runs inside the kernels
+    reason: str = None       # why a fused=True call leaves the fused block (counted in FUSED_FALLBACKS)
+
+
+def route(plan, c_in, B, N, cuda_f32=True, momenta=(), prefer_wide=False, sampling=False):
+    """The path of one call, from the block's `Plan` and plain facts of the call: c_in input channels, B clouds of N
+    points, float32 CUDA tensors or not, the BatchNorms' momenta, PREFER_WIDE, and whether the index stage is handed in
+    (`sampling`).  Attribute and shape checks only: no tensor op, no device sync."""
+    if plan.kind == "stem":
+        return Route(STEM)
+    if not plan.fused:
+        return Route(COMPOSED)
+    if plan.kind == "group_all":
+        return Route(GROUP_ALL)
+    M = N // plan.stride
+    resident = wide = False
+    if plan.mlp is not None and cuda_f32:
+        shapes = (c_in, plan.w1, plan.w2, plan.biased, momenta)
+        resident = fused.covers(B, N, M, plan.K, *shapes) and not prefer_wide
+        wide = fused_wide.covers(B, M, plan.K, *shapes)
+    whole = not plan.res or plan.skip is not None          # any residual branch is one the kernels can take
+    if resident and whole and N <= MAX_SAMPLE_SEQ_POINTS:
+        return Route(RESIDENT, fuse_skip=plan.res)
+    reason = None
+    if wide and not sampling and N > MAX_SAMPLE_SEQ_POINTS:
+        reason = f"N={N} > {MAX_SAMPLE_SEQ_POINTS}: index stage beyond the resident samplers"
+    elif wide and whole:
+        return Route(WIDE, wide=True, fuse_skip=plan.res and fused_wide.lean(c_in, plan.w1[0]))
+    if resident or wide:
+        return Route(GROUPED, wide=not resident, reason=reason)
+    return Route(COMPOSED, reason=f"C_in={c_in} -> {list(plan.widths)}, K={plan.K}: no fused kernel for this shape")
 
 
 def _note_fallback(reason):
@@ -133,160 +192,64 @@ class SetAbstraction(nn.Module):
             if sampler.lower() != 'fps':
                 raise NotImplementedError("only the FPS sampler is on the hot path")
 
-    def _fused_parts(self):
-        """(conv1, bn1, conv2, bn2, relu_after_bn2) if the MLP has the fused kernels' structure."""
-        g = self.grouper
-        if not (isinstance(g, BallGrouper) and g.normalize_dp and len(self.convs) == 2):
-            return None
-        blk1, blk2 = self.convs[0], self.convs[1]
-        if not (len(blk1) == 3 and isinstance(blk1[1], nn.BatchNorm2d) and isinstance(blk1[2], nn.ReLU)
+    def plan(self):
+        """The block's `Plan` (read afresh on every call: modules can be swapped and momenta changed at run time)."""
+        if self.is_head:
+            return Plan("stem", self.fused, None, False, False, None, self.stride, None, ())
+        blocks = [tuple(b) for b in self.convs]          # (unpacked once: indexing an nn.Sequential costs microseconds)
+        widths, K = tuple(b[0].out_channels for b in blocks), getattr(self.grouper, 'nsample', None)
+        if self.all_aggr:
+            return Plan("group_all", self.fused, None, False, False, None, self.stride, K, widths)
+        skip = tuple(self.skipconv) if self.use_res and isinstance(self.skipconv, nn.Sequential) else ()
+        skip = skip[0] if len(skip) == 1 and isinstance(skip[0], nn.Conv1d) and isinstance(self.act, nn.ReLU) else None
+        mlp, relu_after, w1, w2, biased = None, False, None, None, False
+        blk1, blk2 = blocks if len(blocks) == 2 else ((), ())
+        if (isinstance(self.grouper, BallGrouper) and self.grouper.normalize_dp
+                and len(blk1) == 3 and isinstance(blk1[1], nn.BatchNorm2d) and isinstance(blk1[2], nn.ReLU)
                 and len(blk2) in (2, 3) and isinstance(blk2[1], nn.BatchNorm2d)
                 and (len(blk2) == 2 or isinstance(blk2[2], nn.ReLU))):
-            return None
-        return blk1[0], blk1[1], blk2[0], blk2[1], len(blk2) == 3
+            mlp, relu_after = (blk1[0], blk1[1], blk2[0], blk2[1]), len(blk2) == 3
+            w1, w2 = tuple(blk1[0].weight.shape[:2]), tuple(blk2[0].weight.shape[:2])
+            biased = blk1[0].bias is not None or blk2[0].bias is not None
+        return Plan("ball", self.fused, mlp, relu_after, self.use_res, skip, self.stride, K, widths, w1, w2, biased)
 
-    def _resident(self):
-        """Whether this block runs on the register-resident fused kernels (32 -> 32 -> 64, K = 32)."""
-        if not self.fused or self.is_head or self.all_aggr or fused_wide_first():
-            return False
-        parts = self._fused_parts()
-        if parts is None:
-            return False
-        w = parts[0].weight
-        return w.shape[0] == 32 and w.shape[1] == 35 and parts[2].weight.shape[0] == 64 and self.grouper.nsample == 32
+    def route(self, c_in, B, N, cuda_f32=True, sampling=False):
+        """`route` of a call of this block as it stands (its modules, momenta and PREFER_WIDE read now); c_in None:
+        the input channels its conv1 takes."""
+        plan = self.plan()
+        if c_in is None and plan.w1 is not None:
+            c_in = plan.w1[1] - 3
+        momenta = (plan.mlp[1].momentum, plan.mlp[3].momentum) if plan.mlp is not None else ()
+        return plan, route(plan, c_in, B, N, cuda_f32, momenta, PREFER_WIDE, sampling)
 
-    def sample(self, p, out=None):
-        """The block's index stage alone (FPS + ball query; for the register-resident kernels also the
-        neighbourhoods' occurrence statistics) -> adaptpoint_amd.fused.Sampling."""
-        from . import fused
-        return fused.sample_and_query(p, p.shape[1] // self.stride, self.grouper.radius,
-                                      self.grouper.nsample, out=out, geo=self._resident())
-
-    def wide_shapes(self, c_in):
-        """(uses the width-generic kernels for c_in input channels, has a fused residual branch there)."""
-        from . import fused_wide
-        parts = self._fused_parts() if (self.fused and not self.is_head and not self.all_aggr) else None
-        if parts is None:
-            return False, False
-        H = parts[0].weight.shape[0]
-        resident = c_in == 32 and H == 32 and not fused_wide_first()
-        return (not resident) and H in fused_wide.WIDTHS, self._skip_conv1d() is not None and fused_wide.lean(c_in, H)
+    def sample(self, p, out=None, nested=False, ties=None):
+        """The block's index stage alone (FPS + ball query; for the register-resident kernels also the neighbourhoods'
+        occurrence statistics) -> adaptpoint_amd.fused.Sampling.  nested, ties: see `fused.sample_and_query`."""
+        _, r = self.route(None, p.shape[0], p.shape[1], p.is_cuda and p.dtype == torch.float32, True)
+        return fused.sample_and_query(p, p.shape[1] // self.stride, self.grouper.radius, self.grouper.nsample, out=out,
+                                      geo=r.path == RESIDENT, nested=nested, ties=ties)
 
     def index_for(self, smp, n_points, c_in, out=None):
-        """The NeighbourIndex (tile map + inverse map; adaptpoint_amd.fused_wide) of a Sampling of this block:
-        index-stage work, to be run where the Sampling is made.  Stored as smp.index and returned."""
-        from . import fused_wide
-        wide, skip = self.wide_shapes(c_in)
-        if not wide:
-            # the register-resident kernels take the tile map alone
-            if self.fused and not self.is_head and not self.all_aggr and self._fused_parts() is not None and COMPACT_RESIDENT:
-                smp.tmap = fused_wide.tile_map(smp.idx, out=smp.tmap)
-                # ... and the map's row map, for their backward pass (the rows of g_u stored in point-sorted order)
-                B, M = smp.idx.shape[0], smp.idx.shape[1]
-                smp.rowmap = fused_wide.row_map(smp.tmap, B, n_points, M, out=getattr(smp, "rowmap", None), fidx=smp.fidx)
-            return None
-        smp.index = fused_wide.neighbour_index(smp.idx, smp.new_p, n_points, fidx=smp.fidx if skip else None, out=out)
-        return smp.index
-
-    def _skip_conv1d(self):
-        if not self.use_res:
-            return None
-        if (isinstance(self.skipconv, nn.Sequential) and len(self.skipconv) == 1
-                and isinstance(self.skipconv[0], nn.Conv1d) and isinstance(self.act, nn.ReLU)):
-            return self.skipconv[0]
+        """What the block's fused kernels derive from the neighbour indices of a Sampling, for c_in input channels
+        (index-stage work, to be run where the Sampling is made).  The register-resident kernels take the tile map
+        and, for their backward pass, its row map: smp.tmap, smp.rowmap.  The width-generic ones take the
+        NeighbourIndex (tile map + inverse map; adaptpoint_amd.fused_wide), stored as smp.index and returned."""
+        B, M = smp.idx.shape[0], smp.idx.shape[1]
+        _, r = self.route(c_in, B, n_points, smp.idx.is_cuda, True)
+        if r.path == RESIDENT:
+            smp.tmap = fused_wide.tile_map(smp.idx, out=smp.tmap)
+            smp.rowmap = fused_wide.row_map(smp.tmap, B, n_points, M, out=smp.rowmap, fidx=smp.fidx)
+        elif r.path == WIDE:
+            smp.index = fused_wide.neighbour_index(smp.idx, smp.new_p, n_points, fidx=smp.fidx if r.fuse_skip else None,
+                                                   out=out)
+            return smp.index
         return None
-
-    def _wide_block(self, p, f, sampling=None):
-        """The block through the width-generic kernels (adaptpoint_amd.fused_wide), residual branch and final ReLU
-        included when the shape has them fused; None when the configuration is not covered."""
-        from . import fused, fused_wide
-        parts = self._fused_parts()
-        if parts is None or self.all_aggr:
-            return None
-        conv1, bn1, conv2, bn2, relu_after = parts
-        g = self.grouper
-        if not fused_wide.supported(p, f, g.nsample, conv1, conv2, bns=(bn1, bn2), npoint=p.shape[1] // self.stride):
-            return None
-        if sampling is None and p.shape[1] > MAX_SAMPLE_SEQ_POINTS:
-            # the fused index stage (apn_sa_sample_seq) keeps a cloud resident: larger clouds take the unfused operators,
-            # whose FPS is the streaming sampler (csrc/fps.hip: fps_stream_kernel)
-            _note_fallback(f"N={p.shape[1]} > {MAX_SAMPLE_SEQ_POINTS}: index stage beyond the resident samplers")
-            return None
-        C, H = f.shape[1], conv1.weight.shape[0]
-        skip = self._skip_conv1d()
-        if self.use_res and skip is None:
-            return None
-        smp = sampling if sampling is not None else self.sample(p.detach())
-        fuse_skip = skip is not None and fused_wide.lean(C, H)
-        nbr = smp.index
-        if nbr is None or (fuse_skip and nbr.fq is None):
-            nbr = fused_wide.neighbour_index(smp.idx, smp.new_p, p.shape[1], fidx=smp.fidx if fuse_skip else None)
-        new_p = smp.new_p
-        if p.requires_grad:            # the sampled coordinates stay differentiable (the AdaptPoint feedback path)
-            new_p = torch.gather(p, 1, smp.fidx.long().unsqueeze(-1).expand(-1, -1, 3))
-        if fuse_skip or skip is None:
-            out = fused_wide.block(p, new_p, f, nbr, g.radius, conv1, bn1, conv2, bn2, skip_conv=skip,
-                                   relu=(skip is not None) or relu_after, sync_bn=self.sync_bn)
-            return new_p, out
-        pooled = fused_wide.block(p, new_p, f, nbr, g.radius, conv1, bn1, conv2, bn2, relu=False, sync_bn=self.sync_bn)
-        identity = pointwise.run_block(torch.gather(f, -1, smp.fidx.long().unsqueeze(1).expand(-1, C, -1)),
-                                       self.skipconv)
-        return new_p, self.act(pooled + identity)
 
     def sample_many(self, ps, outs=None):
         """Index stages of several batches, FPS of one sharing its launch with the ball query of
         the previous one (adaptpoint_amd.fused.sample_and_query_many)."""
-        from . import fused
         return fused.sample_and_query_many(ps, ps[0].shape[1] // self.stride, self.grouper.radius,
                                            self.grouper.nsample, outs=outs)
-
-    def _fused_block(self, p, f, sampling=None):
-        """The whole block (FPS, ball query, grouped MLP, pool, skip, ReLU) through
-        adaptpoint_amd.fused, or None when the configuration / shapes are not covered."""
-        from . import fused
-        parts = self._fused_parts()
-        if parts is None or self.all_aggr:
-            return None
-        conv1, bn1, conv2, bn2, relu_after = parts
-        g = self.grouper
-        if (not fused.supported(p, f, g.nsample, conv1, conv2, bns=(bn1, bn2),
-                               npoint=p.shape[1] // self.stride) or p.shape[1] > MAX_SAMPLE_SEQ_POINTS
-                or fused_wide_first()):
-            return None
-        skip = None
-        if self.use_res:
-            if not (isinstance(self.skipconv, nn.Sequential) and len(self.skipconv) == 1
-                    and isinstance(self.skipconv[0], nn.Conv1d) and isinstance(self.act, nn.ReLU)):
-                return None
-            skip, relu = self.skipconv[0], True
-        else:
-            relu = relu_after
-        return fused.fused_set_abstraction(p, f, p.shape[1] // self.stride, g.radius, conv1, bn1,
-                                           conv2, bn2, skip, relu, sync_bn=self.sync_bn,
-                                           sampling=sampling)
-
-    def _fused_forward(self, new_p, p, f, idx=None):
-        """max_K convs(cat[dp, f[idx]]) through the fused kernels, or None if unsupported."""
-        from . import fused
-        parts = self._fused_parts()
-        if parts is None:
-            return None
-        conv1, bn1, conv2, bn2, relu_after = parts
-        g = self.grouper
-        from . import fused_wide
-        if idx is None:
-            idx = g.neighbours(new_p, p)
-        if fused.supported(p, f, idx, conv1, conv2, bns=(bn1, bn2)) and not fused_wide_first():
-            out = fused.grouped_mlp_max(p, new_p, f, idx, g.radius, conv1, bn1, conv2, bn2,
-                                        sync_bn=self.sync_bn)
-        elif fused_wide.supported(p, f, idx, conv1, conv2, bns=(bn1, bn2)):
-            out = fused_wide.grouped_mlp_max(p, new_p, f, idx, g.radius, conv1, bn1, conv2, bn2,
-                                             sync_bn=self.sync_bn)
-        else:
-            return None
-        if relu_after:          # activation after the last BN commutes with the max
-            out = self.convs[1][2](out)
-        return out
 
     @staticmethod
     def pool(x):
@@ -294,16 +257,27 @@ class SetAbstraction(nn.Module):
 
     def forward(self, pf, sampling=None):
         p, f = pf
-        if self.is_head:
-            for blk in self.convs:                      # the stem: a 1x1 convolution (csrc/pointwise.hip when fused)
+        plan, r = self.route(f.shape[1], p.shape[0], p.shape[1],
+                             f.is_cuda and f.dtype == torch.float32 and p.dtype == torch.float32, sampling is not None)
+        if r.path == STEM:
+            for blk in self.convs:                      # a 1x1 convolution (csrc/pointwise.hip when fused)
                 f = pointwise.run_block(f, blk, self.fused)
             return p, f
-        if self.fused and not self.all_aggr:
-            res = self._fused_block(p, f, sampling)
-            if res is None:
-                res = self._wide_block(p, f, sampling)
-            if res is not None:
-                return res
+        g, M = self.grouper, p.shape[1] // self.stride
+        if r.path == RESIDENT:
+            return fused.fused_set_abstraction(p, f, M, g.radius, *plan.mlp, plan.skip, plan.res or plan.relu_after,
+                                               sync_bn=self.sync_bn, sampling=sampling)
+        if r.path == WIDE:
+            return self._wide(p, f, plan, r, sampling)
+        if r.path == COMPOSED and r.reason is not None and self.sync_bn and _ranks() > 1:
+            # workloads.sync_batchnorm_ left this block's BatchNorms unconverted because the block exchanges its own
+            # sums; the composed path below would normalise with RANK-LOCAL statistics -- silently not the reference's
+            # SyncBatchNorm (train_autoaug.py:275-282).  Loud instead.
+            raise RuntimeError("SetAbstraction(fused=True, sync_bn=True) cannot run its fused kernels (" + r.reason +
+                               ") and its BatchNorm modules are plain ones: convert them "
+                               "(adaptpoint_amd.dp.convert_sync_batchnorm) or build the block with fused=False")
+        if r.reason is not None:
+            _note_fallback(r.reason)
         idx = None
         if self.all_aggr:
             new_p = p
@@ -312,29 +286,24 @@ class SetAbstraction(nn.Module):
             new_p = (torch.gather(p, 1, picks.unsqueeze(-1).expand(-1, -1, 3)) if p.requires_grad
                      else sampling.new_p)
         else:
-            picks = layers.furthest_point_sample(p, p.shape[1] // self.stride).long()
+            picks = layers.furthest_point_sample(p, M).long()
             new_p = torch.gather(p, 1, picks.unsqueeze(-1).expand(-1, -1, 3))
         identity = None
         if self.use_res:                 # the skip branch sees the sampled points' own features
             identity = self.skipconv(torch.gather(f, -1, picks.unsqueeze(1).expand(-1, f.shape[1], -1)))
-        pooled = self._fused_forward(new_p, p, f, idx) if (self.fused and not self.all_aggr) else None
-        if pooled is None:
-            if self.fused and not self.all_aggr:
-                why = (f"C_in={f.shape[1]} -> {[c[0].out_channels for c in self.convs]}, "
-                       f"K={getattr(self.grouper, 'nsample', None)}: no fused kernel for this shape")
-                if self.sync_bn and _ranks() > 1:
-                    # workloads.sync_batchnorm_ left this block's BatchNorms unconverted because the block exchanges its own
-                    # sums; the composed path below would normalise with RANK-LOCAL statistics -- silently not the reference's
-                    # SyncBatchNorm (train_autoaug.py:275-282).  Loud instead.
-                    raise RuntimeError("SetAbstraction(fused=True, sync_bn=True) cannot run its fused kernels (" + why +
-                                       ") and its BatchNorm modules are plain ones: convert them "
-                                       "(adaptpoint_amd.dp.convert_sync_batchnorm) or build the block with fused=False")
-                _note_fallback(why)
+        if r.path == GROUPED:
+            if idx is None:
+                idx = g.neighbours(new_p, p)
+            pooled = (fused_wide if r.wide else fused).grouped_mlp_max(p, new_p, f, idx, g.radius, *plan.mlp,
+                                                                       sync_bn=self.sync_bn)
+            if plan.relu_after:          # activation after the last BN commutes with the max
+                pooled = self.convs[1][2](pooled)
+        else:
             dp, fj = self.grouper(new_p, p, f, idx) if idx is not None else self.grouper(new_p, p, f)
             x = torch.cat([dp, fj], 1)                                   # 'dp_fj' (group.py:325-326)
-            if self.fused and self.all_aggr and x.shape[2] == 1:
-                # group-all: the "grouped" tensor is (B, C, 1, N) = the points themselves; its 1x1 layers run on
-                # the per-point contraction kernels
+            if r.path == GROUP_ALL:
+                # the "grouped" tensor is (B, C, 1, N) = the points themselves; its 1x1 layers run on the per-point
+                # contraction kernels
                 x = x.squeeze(2)
                 for blk in self.convs:
                     x = pointwise.run_block(x, blk)
@@ -344,3 +313,24 @@ class SetAbstraction(nn.Module):
         if identity is not None:
             pooled = self.act(pooled + identity)
         return new_p, pooled
+
+    def _wide(self, p, f, plan, r, sampling):
+        """The WIDE path: the block through the width-generic kernels (adaptpoint_amd.fused_wide), the residual branch
+        and the final ReLU inside them when `r.fuse_skip`, else the branch composed through csrc/pointwise.hip."""
+        g = self.grouper
+        smp = sampling if sampling is not None else fused.sample_and_query(p.detach(), p.shape[1] // self.stride,
+                                                                            g.radius, g.nsample)
+        nbr = smp.index
+        if nbr is None or (r.fuse_skip and nbr.fq is None):
+            nbr = fused_wide.neighbour_index(smp.idx, smp.new_p, p.shape[1], fidx=smp.fidx if r.fuse_skip else None)
+        new_p = smp.new_p
+        if p.requires_grad:            # the sampled coordinates stay differentiable (the AdaptPoint feedback path)
+            new_p = torch.gather(p, 1, smp.fidx.long().unsqueeze(-1).expand(-1, -1, 3))
+        if r.fuse_skip or not plan.res:
+            out = fused_wide.block(p, new_p, f, nbr, g.radius, *plan.mlp, skip_conv=plan.skip,
+                                   relu=plan.res or plan.relu_after, sync_bn=self.sync_bn)
+            return new_p, out
+        pooled = fused_wide.block(p, new_p, f, nbr, g.radius, *plan.mlp, relu=False, sync_bn=self.sync_bn)
+        identity = pointwise.run_block(torch.gather(f, -1, smp.fidx.long().unsqueeze(1).expand(-1, f.shape[1], -1)),
+                                       self.skipconv)
+        return new_p, self.act(pooled + identity)

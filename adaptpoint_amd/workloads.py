@@ -33,7 +33,8 @@ def sync_batchnorm_(model):
     from .set_abstraction import SetAbstraction
     own = []
     for m in model.modules():
-        if isinstance(m, SetAbstraction) and m.fused and not m.is_head and not m.all_aggr and m._fused_parts() is not None:
+        plan = m.plan() if isinstance(m, SetAbstraction) else None
+        if plan is not None and plan.fused and plan.mlp is not None:      # a block with the fused kernels' structure
             m.sync_bn = True
             own.append(m)
     keep = {id(b) for m in own for b in m.convs.modules() if isinstance(b, torch.nn.modules.batchnorm._BatchNorm)}

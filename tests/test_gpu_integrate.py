@@ -167,7 +167,7 @@ def test_clouds_beyond_the_resident_samplers_go_to_the_reference_forward(dev, mo
             with pytest.raises(AssertionError, match="reference forward reached"):
                 ref([p[:, :1024].double(), fx[:, :, :1024].double()])
         c = dict(integrate.COUNTS)
-        assert c.get(f"SetAbstraction.reference: N > {integrate.MAX_FUSED_POINTS}") == 2, c
+        assert c.get(f"SetAbstraction.reference: N > {SA.MAX_SAMPLE_SEQ_POINTS}") == 2, c
         assert c.get("SetAbstraction.reference: dtype torch.float64 / torch.float64") == 2, c
         assert "SetAbstraction.fused" not in c, c
         # the package's own block: fused=True on a 20000-point cloud runs (unfused index stage + the fused grouped MLP)
