@@ -10,16 +10,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/adaptpoint_amd.h"
+#include "anchor_rotation.h"
 #include "apn_common.h"
 
 namespace apn {
-
-struct AnchorTerms {
-    float th[3], sg[3], tt[3];       // tanh(p0..2), sigmoid(p3..5), tanh(p6..8)
-    float sn[3], cs[3];              // sin / cos of the angles (x, y, z)
-    float s[3];
-    bool unit[3];                    // the scale was 0 and became 1
-};
 
 __device__ __forceinline__ AnchorTerms anchor_terms(const float *p, const float *keep, const float *axes, float r_range,
                                                     float s_range) {
@@ -38,13 +32,6 @@ __device__ __forceinline__ AnchorTerms anchor_terms(const float *p, const float 
         a.s[i] = a.unit[i] ? 1.0f : s;
     }
     return a;
-}
-
-__device__ __forceinline__ void anchor_rotation(const AnchorTerms &a, float (&R)[9]) {
-    const float sx = a.sn[0], sy = a.sn[1], sz = a.sn[2], cx = a.cs[0], cy = a.cs[1], cz = a.cs[2];
-    R[0] = cz * cy; R[1] = cz * sy * sx - sz * cx; R[2] = cz * sy * cx + sz * sx;
-    R[3] = sz * cy; R[4] = sz * sy * sx + cz * cy; R[5] = sz * sy * cx - cz * sx;
-    R[6] = -sy;     R[7] = cy * sx;                R[8] = cy * cx;
 }
 
 __global__ __launch_bounds__(64) void anchor_transforms_kernel(int n, const float *__restrict__ prob,

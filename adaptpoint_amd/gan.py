@@ -62,8 +62,15 @@ class ClassifierStep:
     """One iteration of `train_one_epoch` (train_autoaug.py:471-512) for step_per_update = 1."""
 
     def __init__(self, model, lr=2e-3, weight_decay=0.05, grad_norm_clip=10.0, npoints=1024,
-                 in_channels=4, optimizer=None, grad_sync=None):
+                 in_channels=4, optimizer=None, grad_sync=None, pointwolf=None, rsmix=None):
         self.model = model
+        # pointwolf: an `online_aug.PointWOLF` applied to points[:, :, :3] (in place, as the reference's loop does) before
+        # the resampling -- one iteration of `train_one_epoch_pointwolf` (train_pointwolf_utils.py:25-79).
+        # rsmix: dict(beta, nsample, knn, rsmix_prob) -- one iteration of `train_one_epoch_rsmix` (:90-169): the gate
+        # np.random.rand(1) < rsmix_prob, then `online_aug.rsmix`, and the lambda-weighted loss of the two labels.
+        if pointwolf is not None and rsmix is not None:
+            raise ValueError("ClassifierStep: pointwolf and rsmix are two different trainers; pass one of them")
+        self.pointwolf, self.rsmix = pointwolf, rsmix
         # grad_sync(list of .grad tensors): called before clipping and the optimizer step -- under data parallelism
         # `adaptpoint_amd.dp.allreduce_mean_`, what the reference's DistributedDataParallel wrapper of the classifier
         # does (train_autoaug.py:275-282, with BatchNorm converted to SyncBatchNorm there)
@@ -76,8 +83,23 @@ class ClassifierStep:
         keep this step's autograd graph alive with them (its AccumulateGrad nodes would belong to THIS step's stream; a
         later capture of the step then synchronises with that stream and dies inside hipStreamEndCapture -- graphs.py)."""
         self.model.train()
+        mixed = None
+        if self.pointwolf is not None:
+            _, points[:, :, :3] = self.pointwolf(points[:, :, :3])
+        elif self.rsmix is not None:
+            from .online_aug import rsmix
+            r = np.random.rand(1)
+            if self.rsmix['beta'] > 0 and r < self.rsmix['rsmix_prob']:
+                points, lam, target, target_b = rsmix(points, target, beta=self.rsmix['beta'],
+                                                      n_sample=self.rsmix['nsample'], knn=self.rsmix['knn'])
+                mixed = (lam, target_b)
         pos, x = resample(points, self.npoints, self.in_channels, choice)
-        logits, loss = self.model.get_logits_loss({'pos': pos, 'x': x}, target)
+        if mixed is None:
+            logits, loss = self.model.get_logits_loss({'pos': pos, 'x': x}, target)
+        else:
+            from .online_aug import mixed_loss
+            logits = self.model({'pos': pos, 'x': x})
+            loss = mixed_loss(self.model.criterion, logits, target, mixed[1], mixed[0])
         loss.backward()
         if self.grad_sync is not None:
             self.grad_sync([q.grad for q in self.model.parameters() if q.grad is not None])
@@ -153,12 +175,17 @@ class GanStep:
     the generator step differentiates with respect to the generator's parameters only (the
     reference's `g_loss.backward()` also fills the discriminator's and the classifier's .grad,
     which it then overwrites / zeroes without using); the 4th input channel keeps the real cloud's
-    height, as the in-place `points[:, :, :3] = gen_imgs` leaves it (:155)."""
+    height, as the in-place `points[:, :, :3] = gen_imgs` leaves it (:155).  The PointWOLF call of :143 (whose
+    result the reference only dumps to h5) runs only when a `pointwolf` is given; without one the generator's
+    CPU draws come first in the step.  With one, it runs where the reference runs it, before the generator's draws, and
+    its cloud is returned as 'pointwolf'."""
 
     def __init__(self, generator, discriminator, classifier, criterion, lr_generator=1e-4,
                  lr_discriminator=4e-4, betas=(0.5, 0.999), hard_ratio=3.0, feedback_ratio=1.0,
-                 in_channels=4, batched_feedback=True, capturable=False, grad_sync=None, overlap=False):
+                 in_channels=4, batched_feedback=True, capturable=False, grad_sync=None, overlap=False,
+                 pointwolf=None):
         self.G, self.D, self.C = generator, discriminator, classifier
+        self.pointwolf = pointwolf          # an `online_aug.PointWOLF` (train_autoaug.py:132, 143), or None
         # grad_sync(list of .grad tensors): called before each optimizer step -- under data parallelism
         # `adaptpoint_amd.dp.allreduce_mean_`, what the reference's DistributedDataParallel wrappers of the
         # generator and the discriminator do (train_autoaug.py:98-102; their BatchNorm stays per rank)
@@ -214,6 +241,11 @@ class GanStep:
         xyz = points[:, :, :3].contiguous()
         real_t = torch.full((B, 1), 0.9, device=points.device)
         fake_t = torch.full((B, 1), 0.1, device=points.device)
+
+        pw = None
+        if self.pointwolf is not None:
+            # train_autoaug.py:143, ahead of the generator's draws (device_noise: its draws from the device generator too)
+            _, pw = self.pointwolf(xyz, device_draws=device_noise)
 
         # ---- generator
         if noise is None and device_noise:
@@ -291,5 +323,8 @@ class GanStep:
             self.grad_sync([q.grad for q in D.parameters() if q.grad is not None])
         self.opt_d.step()
         mark("step: end")
-        return {'g_loss_raw': g_raw.detach(), 'feedback_loss': None if fb is None else fb.detach(),
-                'g_loss': g_loss.detach(), 'd_loss': d_loss.detach(), 'gen': gen.detach()}
+        res = {'g_loss_raw': g_raw.detach(), 'feedback_loss': None if fb is None else fb.detach(),
+               'g_loss': g_loss.detach(), 'd_loss': d_loss.detach(), 'gen': gen.detach()}
+        if pw is not None:
+            res['pointwolf'] = pw
+        return res

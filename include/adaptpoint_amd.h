@@ -640,6 +640,27 @@ APN_API int apn_deform_backward(int b, int n, int m, const float *xyz, const flo
                                 const float *mask, float sigma, const float *z, const float *stat, const float *g_out,
                                 float *g_lin, float *g_off, float *g_mask, void *stream);
 
+/* PointWOLF's per-anchor transforms (openpoints/online_aug/pointwolf.py:110-148) from the call's random draws, for
+ * apn_deform_forward: draws = keep (b*m*3) | axis code 1..7 (b*m) | degree (b*m*3) | scale (b*m*3) | translation
+ * (b*m*3) | kernel-axis code 1..7 (b), all float; uniform = 0: the reference's values, uniform = 1: U[0,1) numbers that
+ * the kernel maps onto the same distributions.  -> lin (b,m,3,3) = R diag(s), off (b,m,3), kaxes (b,3) in {0,1}.
+ * One thread per anchor; formulas in csrc/online_aug.hip. */
+APN_API int apn_pointwolf_params(int b, int m, const float *draws, int uniform, float r_range, float s_range,
+                                 float t_range, float *lin, float *off, float *kaxes, void *stream);
+
+/* RSMix (openpoints/online_aug/rsmix_provider.py:161-222), points (b,n,c) float32 with xyz first, c >= 3,
+ * n <= 8192, 0 < nsample < n; draws (3b) int32 = perm | i1 | i2.
+ * _select: 2b selections (s < b: cloud s around point i1[s]; s >= b: cloud perm[s-b] around point i2[s-b]) of the points
+ *   with numpy's float64 expanded squared distance <= r2 (knn_k < 0) or <= its knn_k-th smallest value (knn_k >= 0):
+ *   the first nsample of them in ascending index order -> members (2b, nsample) int32 (-1 past the count), counts (2b).
+ * _mix: per cloud, with |E| = counts[cl] and |A| = counts[b+cl]: the cloud without its erase set, in order, followed by
+ *   |E| rows taken through pick (b, nsample) int32 -- positions in the add list, moved by q1 - q2 in float64 (|A| > 0),
+ *   or rows in [0, n-|E|) of the cloud itself (|A| = 0); out (b,n,c), lam (b) = |E|/n (0 if either set is empty). */
+APN_API int apn_rsmix_select(int b, int n, int c, const float *points, const int *draws, double r2, int knn_k,
+                             int nsample, int *members, int *counts, void *stream);
+APN_API int apn_rsmix_mix(int b, int n, int c, int nsample, const float *points, const int *draws, const int *members,
+                          const int *counts, const int *pick, float *out, float *lam, void *stream);
+
 /* The last layer of the discriminator's group-all stage with its pooling
  * (openpoints/models_adaptpoint/point_discriminator.py:183-189: conv -> ReLU -> max over the cloud's points), fused:
  *   out (B,c_out) = [relu](max_n (w x_b)[o][n] + bias[o]),  idx (B,c_out) int32 = the position of that maximum (the
