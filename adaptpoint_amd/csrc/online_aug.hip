@@ -18,6 +18,7 @@
 #include "../../include/adaptpoint_amd.h"
 #include "anchor_rotation.h"
 #include "apn_common.h"
+#include "lds_bitonic.h"
 
 namespace apn {
 
@@ -139,17 +140,7 @@ __global__ __launch_bounds__(RS_THREADS) void rsmix_select_kernel(int b, int n, 
         for (int p = t; p < P; p += RS_THREADS) sd[p] = p < n ? rs_dist(q, qq, pc + (size_t)p * c) : INFINITY;
         __syncthreads();
         // bitonic sort, ascending: the k-th order statistic, ties and all, as np.sort gives it
-        for (int k = 2; k <= P; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = t; i < (P >> 1); i += RS_THREADS) {
-                    const int lo = 2 * j * (i / j) + (i % j), hi = lo + j;
-                    const double x = sd[lo], y = sd[hi];
-                    const bool up = (lo & k) == 0;
-                    if ((x > y) == up) { sd[lo] = y; sd[hi] = x; }
-                }
-                __syncthreads();
-            }
-        }
+        lds_bitonic_sort<RS_THREADS>(sd, P);
         thr = sd[knn_k];
     }
     int base = 0;

@@ -62,14 +62,23 @@ class ClassifierStep:
     """One iteration of `train_one_epoch` (train_autoaug.py:471-512) for step_per_update = 1."""
 
     def __init__(self, model, lr=2e-3, weight_decay=0.05, grad_norm_clip=10.0, npoints=1024,
-                 in_channels=4, optimizer=None, grad_sync=None, pointwolf=None, rsmix=None):
+                 in_channels=4, optimizer=None, grad_sync=None, pointwolf=None, rsmix=None, wolfmix=None):
         self.model = model
         # pointwolf: an `online_aug.PointWOLF` applied to points[:, :, :3] (in place, as the reference's loop does) before
         # the resampling -- one iteration of `train_one_epoch_pointwolf` (train_pointwolf_utils.py:25-79).
         # rsmix: dict(beta, nsample, knn, rsmix_prob) -- one iteration of `train_one_epoch_rsmix` (:90-169): the gate
         # np.random.rand(1) < rsmix_prob, then `online_aug.rsmix`, and the lambda-weighted loss of the two labels.
+        # wolfmix: dict(pointwolf=PointWOLF, rsmix=dict(...)) -- one iteration of `train_one_epoch_wolfmix` (:180-269):
+        # PointWOLF in place, then the RSMix gate and mix, in one iteration.
         if pointwolf is not None and rsmix is not None:
             raise ValueError("ClassifierStep: pointwolf and rsmix are two different trainers; pass one of them")
+        if wolfmix is not None:
+            if pointwolf is not None or rsmix is not None:
+                raise ValueError("ClassifierStep: wolfmix already holds its pointwolf and rsmix; pass one trainer")
+            if set(wolfmix) != {'pointwolf', 'rsmix'}:
+                raise ValueError("ClassifierStep: wolfmix must be dict(pointwolf=PointWOLF, rsmix=dict(beta, nsample, "
+                                 "knn, rsmix_prob))")
+            pointwolf, rsmix = wolfmix['pointwolf'], wolfmix['rsmix']
         self.pointwolf, self.rsmix = pointwolf, rsmix
         # grad_sync(list of .grad tensors): called before clipping and the optimizer step -- under data parallelism
         # `adaptpoint_amd.dp.allreduce_mean_`, what the reference's DistributedDataParallel wrapper of the classifier
@@ -86,7 +95,7 @@ class ClassifierStep:
         mixed = None
         if self.pointwolf is not None:
             _, points[:, :, :3] = self.pointwolf(points[:, :, :3])
-        elif self.rsmix is not None:
+        if self.rsmix is not None:
             from .online_aug import rsmix
             r = np.random.rand(1)
             if self.rsmix['beta'] > 0 and r < self.rsmix['rsmix_prob']:

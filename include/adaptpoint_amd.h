@@ -661,6 +661,30 @@ APN_API int apn_rsmix_select(int b, int n, int c, const float *points, const int
 APN_API int apn_rsmix_mix(int b, int n, int c, int nsample, const float *points, const int *draws, const int *members,
                           const int *counts, const int *pick, float *out, float *lam, void *stream);
 
+/* The ScanObjectNN dataset transforms of a batch (openpoints/dataset/scanobjectnn/scanobjectnn.py:79-97 with the cfg
+ * chain PointCloudScaling -> PointCloudCenterAndNormalize -> PointCloudRotation), one workgroup per cloud:
+ *   source raw[rows[c], :n] ((s, n_raw, 3) float32, never written; rows NULL: raw[c, :n]), n <= 8192 and n <= n_raw;
+ *   a row outside [0, s) gives a NaN cloud.  Stages by `flags` (APN_CT_*): permute src[perm[i]], scale, heights on
+ *   axis gravity_dim (of the scaled points with APN_CT_HEIGHTS_SCALED, else the unscaled ones), centre, normalise by
+ *   the largest norm, rotate p @ R^T.  -> out (b, n, 4) = [pos, heights].
+ * Host draws: perm (b, n) int32, params (b, 12) float32 = scale (3) | R row-major (9).
+ * Device draws (APN_CT_UNIFORM): uniforms = b*10 per-cloud U[0,1) numbers (scale 3 | mirror 3 | angle 3 | axis order 1)
+ *   followed by b*n per-point ones, whose sorted order is the permutation; cfg (double, 11) = scale_lo, scale_hi,
+ *   mirror (3), scale_xyz (3, 0 = off), angle bounds in radians (3, NaN = None).  perm / params are then unused.
+ * perm_out (b, n) int32 and params_out (b, 12), either may be NULL: the permutation and parameters used. */
+#define APN_CT_PERMUTE 1
+#define APN_CT_SCALE 2
+#define APN_CT_HEIGHTS_SCALED 4
+#define APN_CT_CENTER 8
+#define APN_CT_NORMALIZE 16
+#define APN_CT_ROTATE 32
+#define APN_CT_UNIFORM 64
+#define APN_CT_ANISOTROPIC 128
+#define APN_CT_MIRROR 256
+APN_API int apn_cloud_transform(int b, int n, int n_raw, int s, const float *raw, const int *rows, int flags,
+                                int gravity_dim, const double *cfg, const int *perm, const float *params,
+                                const float *uniforms, int *perm_out, float *params_out, float *out, void *stream);
+
 /* The last layer of the discriminator's group-all stage with its pooling
  * (openpoints/models_adaptpoint/point_discriminator.py:183-189: conv -> ReLU -> max over the cloud's points), fused:
  *   out (B,c_out) = [relu](max_n (w x_b)[o][n] + bias[o]),  idx (B,c_out) int32 = the position of that maximum (the
