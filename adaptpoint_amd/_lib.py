@@ -150,6 +150,7 @@ SIGNATURES = {
     "apn_rsmix_select": [_c_int] * 3 + [_c_void_p] * 2 + [_c_double, _c_int, _c_int] + [_c_void_p] * 3,
     "apn_rsmix_mix": [_c_int] * 4 + [_c_void_p] * 8,
     "apn_cloud_transform": [_c_int] * 4 + [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 8,
+    "apn_cls_confusion": [_c_int] * 2 + [_c_void_p, _c_int] + [_c_void_p] * 5,
 }
 
 _lib = None

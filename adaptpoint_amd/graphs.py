@@ -55,6 +55,9 @@ def _lib():
         _hip.hipGraphNodeGetType.restype = ctypes.c_int
         _hip.hipGraphChildGraphNodeGetGraph.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
         _hip.hipGraphChildGraphNodeGetGraph.restype = ctypes.c_int
+        _hip.hipGraphGetEdges.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.POINTER(ctypes.c_size_t)]
+        _hip.hipGraphGetEdges.restype = ctypes.c_int
     return _hip
 
 
@@ -93,6 +96,26 @@ def _census_raw(raw, census, depth):
                 raise RuntimeError(f"hipGraphChildGraphNodeGetGraph failed ({rc})")
             _census_raw(child, census, depth + 1)
     return census
+
+
+def is_chain(graph):
+    """True when the top level of a graph captured into `new_graph()` is one chain of nodes -- what a single stream
+    captures: no node has more than one predecessor or successor, so nothing in it can run beside anything else."""
+    hip = _lib()
+    raw = ctypes.c_void_p(graph.raw_cuda_graph())
+    n = ctypes.c_size_t(0)
+    if hip.hipGraphGetNodes(raw, None, ctypes.byref(n)) != 0:
+        raise RuntimeError("hipGraphGetNodes failed")
+    e = ctypes.c_size_t(0)
+    if hip.hipGraphGetEdges(raw, None, None, ctypes.byref(e)) != 0:
+        raise RuntimeError("hipGraphGetEdges failed")
+    if e.value == 0:
+        return n.value <= 1
+    src, dst = (ctypes.c_void_p * e.value)(), (ctypes.c_void_p * e.value)()
+    if hip.hipGraphGetEdges(raw, src, dst, ctypes.byref(e)) != 0:
+        raise RuntimeError("hipGraphGetEdges failed")
+    outs, ins = [src[i] for i in range(e.value)], [dst[i] for i in range(e.value)]
+    return e.value == n.value - 1 and len(set(outs)) == len(outs) and len(set(ins)) == len(ins)
 
 
 def assert_replayable(graph, what="captured graph"):

@@ -685,6 +685,19 @@ APN_API int apn_cloud_transform(int b, int n, int n_raw, int s, const float *raw
                                 int gravity_dim, const double *cfg, const int *perm, const float *params,
                                 const float *uniforms, int *perm_out, float *params_out, float *out, void *stream);
 
+/* The classification metric of an evaluation batch (openpoints/utils/metrics.py:62-73 fed `logits.argmax(dim=1)`), one
+ * launch, no host read:
+ *   logits (b, k) float32 with row stride ld >= k; target (b,) int32; valid: a device int32 scalar -- only rows
+ *   r < clamp(*valid, 0, b) are counted (NULL: all b), so one captured graph also serves a padded last batch.
+ *   pred (b,) int32, may be NULL: the argmax of EVERY row, padding rows included, by torch.argmax's rule (the first
+ *   index of the maximum; a NaN beats every number and the first NaN wins; an all -inf row gives 0).
+ *   cm: k*k + 1 counters, added to and never cleared: cell t*k + p for target t and prediction p (torch.bincount's
+ *   layout); the last cell counts counted rows whose target lies outside [0, k).
+ * The one exception to this header's int32 / float32 contract: cm holds unsigned 64-bit counts, as bincount's are.
+ * Integer atomics: exact and the same on every run. */
+APN_API int apn_cls_confusion(int b, int k, const float *logits, int ld, const int *target, const int *valid,
+                              unsigned long long *cm, int *pred, void *stream);
+
 /* The last layer of the discriminator's group-all stage with its pooling
  * (openpoints/models_adaptpoint/point_discriminator.py:183-189: conv -> ReLU -> max over the cloud's points), fused:
  *   out (B,c_out) = [relu](max_n (w x_b)[o][n] + bias[o]),  idx (B,c_out) int32 = the position of that maximum (the
