@@ -204,13 +204,13 @@ class AdaptPointAugmentor(nn.Module):
     """generator_component4_15.py:119-181 (`AdaptPoint_Augmentor`; cfg keys of
     cfgs/scanobjectnn/pointnext-s_adaptpoint_1.yaml:50-56)."""
 
-    def __init__(self, w_num_anchor=4, w_sigma=0.5, w_R_range=10, w_S_range=3, w_T_range=0.25, fused=True):
+    def __init__(self, w_num_anchor=4, w_sigma=0.5, w_R_range=10, w_S_range=3, w_T_range=0.25, fused=True, hoisted=False):
         super().__init__()
         self.num_anchor = w_num_anchor
         self.sigma = w_sigma
         self.w_R_range, self.w_S_range, self.w_T_range = w_R_range, w_S_range, w_T_range
         self.fused = fused
-        self.predict_prob_layer = SAComponent(fused=fused)
+        self.predict_prob_layer = SAComponent(fused=fused, hoisted=hoisted)
 
     def forward(self, xyz, noise: Optional[Noise] = None):
         """xyz (B,N,3) -> (xyz, augmented (B,N,3)).  `noise`: the call's random draws (default:

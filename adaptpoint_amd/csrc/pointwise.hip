@@ -276,9 +276,11 @@ constexpr int pw_lds_bytes() { return 2 * 2 * NS * PW_T * PW_ROW * 2 + 4 * 2 * P
 // LDS writes of this wave done, then the workgroup's rendezvous (global loads stay in flight across it)
 __device__ __forceinline__ void pw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// The kernel's body for workgroup (bx, by, bz) of a (gdx, gdy, gdz) grid of tiles: pw_gemm_kernel hands it its own
+// block index, pw_gemm2_kernel the index inside the problem the workgroup belongs to.
 template <bool A_KC, bool B_KC, int NS>
-__global__ __launch_bounds__(512, 1) void pw_gemm_kernel(PwGemm g) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char pw_lds[];
+__device__ __forceinline__ void pw_gemm_body(const PwGemm &g, unsigned char *pw_lds, unsigned bx, unsigned by, unsigned bz,
+                                             unsigned gdx, unsigned gdy, unsigned gdz) {
     constexpr int TILE = NS * PW_T * PW_ROW;                       // bf16 per operand tile
     __bf16 *lds = reinterpret_cast<__bf16 *>(pw_lds);              // [buffer][A | B][plane][row][k]
     float (*red)[2][PW_T] = reinterpret_cast<float (*)[2][PW_T]>(pw_lds + 2 * 2 * TILE * 2);
@@ -289,14 +291,14 @@ __global__ __launch_bounds__(512, 1) void pw_gemm_kernel(PwGemm g) {
     // its L2 under round-robin placement (a speed assumption only); dealt out in launch order the tiles of one batch entry
     // -- which read the same operand slices -- went to all eight XCDs and each pulled the slice through its own L2.  Here
     // all gridDim.x * gridDim.y tiles of an entry run on one XCD.
-    int bxi = blockIdx.x, byi = blockIdx.y, bzi = blockIdx.z;
-    if ((gridDim.z & 7u) == 0u) {
-        const unsigned per = gridDim.x * gridDim.y;
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    int bxi = bx, byi = by, bzi = bz;
+    if ((gdz & 7u) == 0u) {
+        const unsigned per = gdx * gdy;
+        const unsigned lin = bx + gdx * (by + gdy * bz);
         const unsigned slot = lin >> 3, w = slot % per;
         bzi = (int)((slot / per) * 8u + (lin & 7u));
-        bxi = (int)(w % gridDim.x);
-        byi = (int)(w / gridDim.x);
+        bxi = (int)(w % gdx);
+        byi = (int)(w / gdx);
     }
     const int R0 = byi * PW_T, Q0 = bxi * PW_T, z = bzi;
     PwLoader<A_KC> la;
@@ -476,7 +478,7 @@ __global__ __launch_bounds__(512, 1) void pw_gemm_kernel(PwGemm g) {
                 const float cand = red[w][0][t];
                 if (cand > best) { best = cand; bi = reinterpret_cast<int *>(&red[w][1][0])[t]; }
             }
-            const size_t o = ((size_t)z * gridDim.x + bxi) * g.R + R0 + t;
+            const size_t o = ((size_t)z * gdx + bxi) * g.R + R0 + t;
             g.pool_val[o] = best;
             g.pool_idx[o] = bi;
         }
@@ -547,7 +549,7 @@ __global__ __launch_bounds__(512, 1) void pw_gemm_kernel(PwGemm g) {
             double m2 = 0.0;
 #pragma unroll
             for (int w = 0; w < 4; ++w) m2 += m2w[w] + 32.0 * (mw[w] - mean) * (mw[w] - mean);
-            float *dst = g.part + ((size_t)z * gridDim.x + bxi) * 2 * g.R + R0 + t;
+            float *dst = g.part + ((size_t)z * gdx + bxi) * 2 * g.R + R0 + t;
             dst[0] = (float)(mean * 128.0);
             dst[g.R] = (float)(m2 < 0.0 ? 0.0 : m2);
         } else if (t < PW_T && R0 + t < g.R) {
@@ -565,12 +567,40 @@ __global__ __launch_bounds__(512, 1) void pw_gemm_kernel(PwGemm g) {
                     n = tot;
                 }
             }
-            float *dst = g.part + ((size_t)z * gridDim.x + bxi) * 2 * g.R + R0 + t;
+            float *dst = g.part + ((size_t)z * gdx + bxi) * 2 * g.R + R0 + t;
             dst[0] = (float)(mean * n);
             dst[g.R] = (float)(m2 < 0.0 ? 0.0 : m2);
         }
     }
     pw_stamp(4);
+}
+
+
+template <bool A_KC, bool B_KC, int NS>
+__global__ __launch_bounds__(512, 1) void pw_gemm_kernel(PwGemm g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pw_lds[];
+    pw_gemm_body<A_KC, B_KC, NS>(g, pw_lds, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
+}
+
+// TWO problems of one operand form in one launch: a flat grid that is problem 0's tile grid followed by problem 1's; the
+// workgroup index picks the problem (uniform over the workgroup), everything after that is pw_gemm_kernel.  For pairs of
+// products that depend on the same inputs and each fill less than the chip (the hoisted feature-propagation block: the
+// skip product beside the coarse-level product, forward and in both gradients): side by side the launch ends with the
+// longer of the two contraction loops instead of their sum.
+struct PwGemm2 {
+    PwGemm g[2];
+    unsigned gdx[2], gdy[2], gdz[2];
+    unsigned first;           // workgroups of problem 0
+};
+
+template <bool A_KC, bool B_KC, int NS>
+__global__ __launch_bounds__(512, 1) void pw_gemm2_kernel(PwGemm2 gg) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pw_lds[];
+    const int p = blockIdx.x >= gg.first ? 1 : 0;
+    const unsigned lin = blockIdx.x - (p ? gg.first : 0u);
+    const unsigned gdx = gg.gdx[p], gdy = gg.gdy[p];
+    const unsigned bx = lin % gdx, rest = lin / gdx;
+    pw_gemm_body<A_KC, B_KC, NS>(gg.g[p], pw_lds, bx, rest % gdy, rest / gdy, gdx, gdy, gg.gdz[p]);
 }
 
 // sum of one double per thread over the workgroup, returned to every thread
@@ -817,6 +847,31 @@ __global__ __launch_bounds__(256) void pw_fold_kernel(const float *__restrict__ 
     red[q][threadIdx.x & 63] = s;
     __syncthreads();
     if (q == 0 && e < n) out[e] = (float)((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+}
+
+// pw_fold_kernel for the two blocks of apn_pw_contract2 in one launch (blockIdx.y picks the block), each folded in
+// pw_fold_kernel's order into an (r x q) block of a wider matrix: out[i * ldo + j] = sum_s part[s][i][j]
+struct PwFold2 {
+    const float *part[2];
+    float *out[2];
+    int splits[2], r[2], q[2], ldo[2];
+};
+__global__ __launch_bounds__(256) void pw_fold2_kernel(PwFold2 f) {
+    __shared__ double red[4][64];
+    const int p = blockIdx.y;
+    const size_t n = (size_t)f.r[p] * f.q[p];
+    const size_t e = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    const int k0 = threadIdx.x >> 6, splits = f.splits[p];
+    const float *part = f.part[p];
+    double s = 0.0;
+    if (e < n)
+        for (int k = k0; k < splits; k += 4) s += (double)part[(size_t)k * n + e];
+    red[k0][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (k0 == 0 && e < n) {
+        const size_t i = e / f.q[p], j = e - i * f.q[p];
+        f.out[p][i * f.ldo[p] + j] = (float)((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+    }
 }
 
 // ---- convolution + bias + ReLU + max over the points of a cloud (the last layer of the discriminator's group-all
@@ -1187,6 +1242,112 @@ extern "C" int apn_pw_contract(int nbatch, int r, int q, int k, const float *a, 
         const size_t ne = (size_t)r * q;
         hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)((ne + 63) / 64)), dim3(256), 0, (hipStream_t)stream, scratch,
                            splits, ne, d);
+        APN_LAUNCH_CHECK();
+    }
+    return APN_OK;
+}
+
+// Two products of the same operand form as ONE launch (pw_gemm2_kernel): problem p is apn_pw_contract's
+// (nbatch, r, q, k, a, b, d, splits, scratch) with splits[p] == 0 (d[p][z] = a[z] b[z], leading dimension ldd[p]) or
+// splits[p] > 0 (d[p] = sum_z a[z] b[z] in splits[p] fixed-order shares; scratch[p] holds [splits][r][q]; the fold --
+// one launch for both problems -- writes the (r x q) result with leading dimension ldd[p], so that the two results may
+// be column blocks of one matrix).  Both problems split or neither.  The problem whose workgroups walk the longer
+// contraction loop is placed first in the grid; the results do not depend on the placement.
+template <bool AK, bool BK, int NS>
+static int pw_launch2(unsigned blocks, const apn::PwGemm2 &gg, hipStream_t stream) {
+    using namespace apn;
+    static DynLdsOnce configured;
+    if (hipError_t e = set_dyn_lds(configured, (const void *)pw_gemm2_kernel<AK, BK, NS>, pw_lds_bytes<NS>())) return (int)e;
+    hipLaunchKernelGGL((pw_gemm2_kernel<AK, BK, NS>), dim3(blocks), dim3(512), pw_lds_bytes<NS>(), stream, gg);
+    APN_LAUNCH_CHECK();
+    return APN_OK;
+}
+
+#define PW_LAUNCH2(AK, BK, blocks, gg)                                                                          \
+    do {                                                                                                        \
+        const int rc__ = precision == 3 ? pw_launch2<AK, BK, 3>(blocks, gg, (hipStream_t)stream)               \
+                                        : pw_launch2<AK, BK, 2>(blocks, gg, (hipStream_t)stream);              \
+        if (rc__) return rc__;                                                                                  \
+    } while (0)
+
+// shares for the split form of a pair: together at most one round of the 256 CUs, divided so that the workgroups of both
+// problems walk about the same number of chunks (s_p proportional to the problem's chunks), within pw_weight_splits' caps
+extern "C" int apn_pw_contract2_splits(int which, int nbatch0, int r0, int q0, int k0, int nbatch1, int r1, int q1, int k1) {
+    using namespace apn;
+    if (nbatch0 <= 0 || r0 <= 0 || q0 <= 0 || k0 <= 0 || nbatch1 <= 0 || r1 <= 0 || q1 <= 0 || k1 <= 0) return 1;
+    const long long tiles[2] = {(long long)((r0 + PW_T - 1) / PW_T) * ((q0 + PW_T - 1) / PW_T),
+                                (long long)((r1 + PW_T - 1) / PW_T) * ((q1 + PW_T - 1) / PW_T)};
+    const long long total[2] = {(long long)nbatch0 * ((k0 + PW_KC - 1) / PW_KC), (long long)nbatch1 * ((k1 + PW_KC - 1) / PW_KC)};
+    const int p = which ? 1 : 0;
+    long long s = 256 * total[p] / (tiles[0] * total[0] + tiles[1] * total[1]);
+    const long long cap = total[p] >= 64 ? total[p] / 8 : total[p] / 2;
+    if (s > cap) s = cap;
+    if (s < 1) s = 1;
+    return (int)s;
+}
+
+extern "C" int apn_pw_contract2(int a_kcont, int b_kcont, int precision, const int *nbatch, const int *r, const int *q,
+                                const int *k, const float *const *a, const long long *a_batch, const int *lda,
+                                const float *const *b, const long long *b_batch, const int *ldb, float *const *d,
+                                const long long *d_batch, const int *ldd, const int *splits, float *const *scratch,
+                                void *stream) {
+    using namespace apn;
+    if (!nbatch || !r || !q || !k || !a || !a_batch || !lda || !b || !b_batch || !ldb || !d || !d_batch || !ldd || !splits ||
+        !scratch || (precision != 2 && precision != 3))
+        return APN_EINVAL;
+    if ((splits[0] > 0) != (splits[1] > 0)) return APN_EINVAL;
+    PwGemm2 gg{};
+    unsigned count[2];
+    // the longer loop first: its workgroups are dealt out before the short ones when the grid exceeds the chip
+    const long long len0 = splits[0] > 0 ? ((long long)nbatch[0] * ((k[0] + PW_KC - 1) / PW_KC) + splits[0] - 1) / (splits[0] > 0 ? splits[0] : 1)
+                                         : (k[0] + PW_KC - 1) / PW_KC;
+    const long long len1 = splits[1] > 0 ? ((long long)nbatch[1] * ((k[1] + PW_KC - 1) / PW_KC) + splits[1] - 1) / (splits[1] > 0 ? splits[1] : 1)
+                                         : (k[1] + PW_KC - 1) / PW_KC;
+    const int order[2] = {len1 > len0 ? 1 : 0, len1 > len0 ? 0 : 1};
+    for (int slot = 0; slot < 2; ++slot) {
+        const int p = order[slot];
+        if (nbatch[p] <= 0 || r[p] <= 0 || q[p] <= 0 || k[p] <= 0 || nbatch[p] > 65535 || !a[p] || !b[p] || !d[p] || splits[p] < 0 ||
+            (splits[p] > 0 && !scratch[p]) || ldd[p] < q[p])
+            return APN_EINVAL;
+        PwGemm &g = gg.g[slot];
+        g.A = PwOperand{a[p], a_batch[p], lda[p]};
+        g.B = PwOperand{b[p], b_batch[p], ldb[p]};
+        g.R = r[p]; g.Q = q[p]; g.K = k[p];
+        g.cpb = (k[p] + PW_KC - 1) / PW_KC;
+        g.total = nbatch[p] * g.cpb;
+        g.a_vec = a_kcont ? pw_vec(a[p], a_batch[p], lda[p], k[p], r[p]) : pw_vec_rows(a[p], a_batch[p], lda[p], r[p], k[p]);
+        g.b_vec = b_kcont ? pw_vec(b[p], b_batch[p], ldb[p], k[p], q[p]) : pw_vec_rows(b[p], b_batch[p], ldb[p], q[p], k[p]);
+        int nz = nbatch[p];
+        if (splits[p] > 0) {
+            g.D = scratch[p]; g.d_batch = (long long)r[p] * q[p]; g.ldd = q[p];
+            g.cps = (g.total + splits[p] - 1) / splits[p];
+            nz = splits[p];
+        } else {
+            g.D = d[p]; g.d_batch = d_batch[p]; g.ldd = ldd[p];
+            g.cps = g.cpb;
+        }
+        gg.gdx[slot] = (q[p] + PW_T - 1) / PW_T;
+        gg.gdy[slot] = (r[p] + PW_T - 1) / PW_T;
+        gg.gdz[slot] = nz;
+        const unsigned long long cnt = (unsigned long long)gg.gdx[slot] * gg.gdy[slot] * nz;
+        if (cnt > 0x3FFFFFFFull) return APN_EINVAL;
+        count[slot] = (unsigned)cnt;
+    }
+    gg.first = count[0];
+    const unsigned blocks = count[0] + count[1];
+    if (a_kcont && b_kcont) PW_LAUNCH2(true, true, blocks, gg);
+    else if (a_kcont) PW_LAUNCH2(true, false, blocks, gg);
+    else if (b_kcont) PW_LAUNCH2(false, true, blocks, gg);
+    else PW_LAUNCH2(false, false, blocks, gg);
+    if (splits[0] > 0) {
+        PwFold2 f{};
+        size_t ne = 0;
+        for (int p = 0; p < 2; ++p) {
+            f.part[p] = scratch[p]; f.out[p] = d[p]; f.splits[p] = splits[p]; f.r[p] = r[p]; f.q[p] = q[p]; f.ldo[p] = ldd[p];
+            const size_t n = (size_t)r[p] * q[p];
+            ne = n > ne ? n : ne;
+        }
+        hipLaunchKernelGGL(pw_fold2_kernel, dim3((unsigned)((ne + 63) / 64), 2), dim3(256), 0, (hipStream_t)stream, f);
         APN_LAUNCH_CHECK();
     }
     return APN_OK;

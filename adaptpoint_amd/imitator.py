@@ -18,7 +18,8 @@ from .attention import AnchorSelfAttention
 from . import graphs
 from .graphs import mark, mark_grad
 from . import pointwise
-from .layers import inverse_distance_weights, three_interpolate, three_interpolation, three_nn
+from . import propagation
+from .layers import inverse_distance_weights, three_interpolate, three_interpolation, three_nn, three_nn_weights
 from .pointset import PointsetGrouper
 
 
@@ -62,15 +63,24 @@ class ConvBNReLU1D(nn.Module):
 
 
 class PointNetFeaturePropagation(nn.Module):
-    """(:330-366)"""
+    """(:330-366).  `hoisted`: the block in the form of adaptpoint_amd.propagation -- the convolution applied to the
+    coarse features before the interpolation, W [p1 ; blend(p2)] = W[:, :C1] p1 + blend(W[:, C1:] p2): same
+    parameters, same state_dict."""
 
     def __init__(self, in_channel, out_channel, blocks=1, groups=1, res_expansion=1.0, bias=False,
-                 activation='relu', fused=True):
+                 activation='relu', fused=True, hoisted=False):
         super().__init__()
         self.fuse = ConvBNReLU1D(in_channel, out_channel, 1, bias=bias, fused=fused)
+        self.hoisted = hoisted
 
     def forward(self, xyz1, xyz2, points1, points2, nearest=None):
         """nearest: (indices, weights) of `three_nn` + `inverse_distance_weights` computed ahead (index work)."""
+        if self.hoisted:
+            if nearest is None:
+                nearest = three_nn_weights(xyz1.contiguous(), xyz2.contiguous())
+            return propagation.propagate(None if points1 is None else points1.contiguous(), points2.contiguous(),
+                                         nearest[0], nearest[1], self.fuse.net[0], self.fuse.net[1], relu=True,
+                                         kernels=self.fuse.fused)
         if nearest is None:
             interpolated = three_interpolation(xyz1, xyz2, points2)
         else:
@@ -108,7 +118,7 @@ class SAComponent(nn.Module):
 
     def __init__(self, in_channel=3, embed_dim=64, res_expansion=1.0, activation="relu", bias=False,
                  normalize="anchor", dim_expansion=(2, 2, 2, 2), radii=(0.1, 0.2, 0.4, 0.8),
-                 k_neighbors=(24, 24, 24, 24), reducers=(2, 2, 2, 2), fused=True, **kwargs):
+                 k_neighbors=(24, 24, 24, 24), reducers=(2, 2, 2, 2), fused=True, hoisted=False, **kwargs):
         super().__init__()
         self.stages = len(dim_expansion)
         self.embedding = ConvBNReLU1D(in_channel, embed_dim, bias=bias, activation=activation, fused=fused)
@@ -129,7 +139,8 @@ class SAComponent(nn.Module):
         self.decode_list = nn.ModuleList(
             PointNetFeaturePropagation(channels[-(i + 1)] + channels[-(i + 2)], channels[-(i + 2)],
                                        blocks=1, groups=1, res_expansion=res_expansion, bias=bias,
-                                       activation=activation, fused=fused) for i in range(self.stages))
+                                       activation=activation, fused=fused, hoisted=hoisted)
+            for i in range(self.stages))
         self.localfeat_mask_selfattention = AnchorSelfAttention(dim=embed_dim, head_num=4, fused=fused)
         self.extract_local_feat_masking = nn.Sequential(nn.Conv1d(embed_dim, 3, 1, bias=False), nn.BatchNorm1d(3))
         self.extract_global_feat_masking = nn.Sequential(nn.Conv1d(last, 3, 1, bias=False), nn.BatchNorm1d(3))

@@ -19,7 +19,8 @@ checks exactly that equality), which makes these blocks the module-level consume
 import torch
 import torch.nn as nn
 
-from .layers import furthest_point_sample, gather_operation, make_grouper, three_interpolation
+from . import propagation
+from .layers import furthest_point_sample, gather_operation, make_grouper, three_interpolation, three_nn_weights
 from .set_abstraction import _act, convblock
 
 
@@ -99,16 +100,26 @@ class SetAbstractionMSG(nn.Module):
 
 
 class FeaturePropagation2(nn.Module):
-    """pointnetv2.py:108-150."""
+    """pointnetv2.py:108-150.  `hoisted`: the first block in adaptpoint_amd.propagation's form, where it is a 1x1
+    convolution + BatchNorm (+ ReLU) and the coarse level has coordinates; today's path otherwise."""
 
-    def __init__(self, mlp, norm_args=None, act_args=None):
+    def __init__(self, mlp, norm_args=None, act_args=None, hoisted=False):
         super().__init__()
+        self.hoisted = hoisted
         norm_args = {'norm': 'bn1d'} if norm_args is None else norm_args
         act_args = {'act': 'relu'} if act_args is None else act_args
         self.convs = nn.Sequential(*[convblock(mlp[i], mlp[i + 1], 1, norm_args=norm_args, act_args=act_args)
                                      for i in range(len(mlp) - 1)])
 
     def forward(self, unknown, known, unknown_feats, known_feats):
+        parts = propagation.block_parts(self.convs[0]) if (self.hoisted and known is not None) else None
+        if parts is not None:
+            nearest, weights = three_nn_weights(unknown.contiguous(), known.contiguous())
+            f = propagation.propagate(None if unknown_feats is None else unknown_feats.contiguous(), known_feats.contiguous(),
+                                      nearest, weights, *parts)
+            for block in list(self.convs)[1:]:
+                f = block(f)
+            return f
         if known is not None:
             up = three_interpolation(unknown, known, known_feats)
         else:

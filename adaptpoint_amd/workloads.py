@@ -95,10 +95,11 @@ def _clouds(batch, npoints, seed):
 
 
 def build(workload, dev, batch=32, npoints=1024, fused=True, distributed=None, capturable=False, overlap=False,
-          seed=0, name_seeded=False, dropout=True, noise_on_device=None, classes=15, record_grads=False):
+          seed=0, name_seeded=False, dropout=True, noise_on_device=None, classes=15, record_grads=False, hoisted=False):
     """-> Job.  distributed: None = follow torch.distributed's state.  capturable: optimizer state on the device and
     the generator's draws from the device generator, so that `step()` can be captured into a hipGraph.  name_seeded:
-    `fill_parameters_by_name` weights (tests); else `torch.manual_seed(seed)` initialisation, identical on every rank."""
+    `fill_parameters_by_name` weights (tests); else `torch.manual_seed(seed)` initialisation, identical on every rank.  hoisted: the generator's
+    feature-propagation decoders in the form of adaptpoint_amd.propagation."""
     from .augmentor import AdaptPointAugmentor
     from .discriminator import PointDiscriminator1
     from .gan import ClassifierStep, GanStep
@@ -145,7 +146,7 @@ def build(workload, dev, batch=32, npoints=1024, fused=True, distributed=None, c
         job.cls_step = ClassifierStep(C, npoints=1024 if npoints > 1024 else npoints, optimizer=opt_c,
                                       grad_sync=sync("classifier"))
     if workload in ("gan", "adaptpoint"):
-        G = mk(AdaptPointAugmentor(fused=fused)).to(dev)
+        G = mk(AdaptPointAugmentor(fused=fused, hoisted=hoisted)).to(dev)
         D = mk(PointDiscriminator1(num_classes=classes, fused=fused)).to(dev)
         if not dropout:
             D.drop1.p = D.drop2.p = 0.0

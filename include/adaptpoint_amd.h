@@ -611,6 +611,38 @@ APN_API int apn_pw_contract_splits(int nbatch, int r, int q, int k);
 APN_API int apn_pw_contract(int nbatch, int r, int q, int k, const float *a, long long a_batch, int lda, int a_kcont,
                             const float *b, long long b_batch, int ldb, int b_kcont, float *d, long long d_batch, int ldd,
                             int splits, float *scratch, int precision, void *stream);
+/* TWO such products of the same operand form (a_kcont, b_kcont shared) as ONE launch: a grid that is the concatenation
+ * of both problems' 128 x 128 tile grids, the problem picked from the workgroup index.  Every array argument has two
+ * entries, problem p described as for apn_pw_contract.  splits[p] == 0 for both: d[p][z] = a[p][z] b[p][z] with leading
+ * dimension ldd[p].  splits[p] > 0 for both (apn_pw_contract2_splits(p, ...)): d[p] = sum_z a[p][z] b[p][z] in
+ * splits[p] shares (scratch[p]: [splits[p]][r][q]) added in a fixed order by one fold launch that writes the r x q result
+ * with leading dimension ldd[p] >= q[p] -- the two results may be column blocks of one matrix.  The fast loaders need
+ * 16-byte aligned operand origins, rows and batch strides; anything else takes the value-by-value loads (correct, slower).
+ * For pairs that each fill less than the chip (the hoisted feature-propagation block, csrc/feature_prop.hip). */
+APN_API int apn_pw_contract2_splits(int which, int nbatch0, int r0, int q0, int k0, int nbatch1, int r1, int q1, int k1);
+APN_API int apn_pw_contract2(int a_kcont, int b_kcont, int precision, const int *nbatch, const int *r, const int *q,
+                             const int *k, const float *const *a, const long long *a_batch, const int *lda,
+                             const float *const *b, const long long *b_batch, const int *ldb, float *const *d,
+                             const long long *d_batch, const int *ldd, const int *splits, float *const *scratch,
+                             void *stream);
+
+/* Feature propagation with its convolution hoisted to the coarse points (csrc/feature_prop.hip): what follows the two
+ * products a = W[:, :C1] f1 (B,O,n) and u = W[:, C1:] f2 (B,O,m):
+ *     y[b][o][i] = a[b][o][i] + sum_{j<3} weight[b][i][j] * u[b][o][idx[b][i][j]]
+ * a may be null (no skip features); idx / weight (B,n,3) as apn_three_nn + apn_three_nn_weights leave them; y may alias a.
+ * training != 0: y and part are written -- part [apn_pw_conv_tiles(b, n)][2][o], BatchNorm's partial statistics in the
+ *   layout apn_pw_bn_act folds ({sum, M2 around the tile's mean} per 128 columns of a cloud); apn_pw_bn_act follows.
+ * training == 0: out = [relu](scale y + shift) from the running statistics (gamma / beta may be null) in the same launch;
+ *   y (the pre-activation, what apn_pw_bn_act_grad reads) and stat [4][o] are written when not null.
+ * Fixed-order sums only: results are bit-identical from run to run.
+ * idx is TRUSTED to lie in [0, m), as apn_three_interpolate trusts it: it is not validated (an index outside is clamped
+ * into the row, so it reads a wrong element, never memory outside u).
+ * Negative sizes, b > 65535 or a missing pointer -> APN_EINVAL; b, o or n == 0 -> APN_OK without a launch. */
+APN_API int apn_fp_blend_stats(int b, int o, int m, int n, const float *a, const float *u, const int *idx,
+                               const float *weight, float *y, float *part, int training, const float *gamma,
+                               const float *beta, const float *run_mean, const float *run_var, float eps, int relu,
+                               float *stat, float *out, void *stream);
+
 /* out[z][j][i] = in[z][i][j] for in (nbatch, r, c) float32, contiguous: the layout change between the per-point layers'
  * (B, C, N) and the grouper's / attention's (B, N, C) (generator_component4_15.py:650-657 permutes and lets PyTorch copy). */
 APN_API int apn_pw_transpose(int nbatch, int r, int c, const float *in, float *out, void *stream);

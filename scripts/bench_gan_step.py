@@ -2,14 +2,16 @@
 + discriminator + feedback through the eval-mode PointNeXt-S classifier -- one `train_gan`
 iteration (examples/classification/train_autoaug.py:133-204), B=32, one MI355X.
 
-    python scripts/bench_gan_step.py [--points 1024|2048] [--batch 32] [--mode fused|composed|both]
+    python scripts/bench_gan_step.py [--points 1024|2048] [--batch 32] [--mode fused|composed|both] [--hoisted]
 
 N=1024 is what BASELINE.json states; N=2048 is what the reference trains at (SURVEY header).
 `fused`: the fused operators everywhere they exist (grouper, attention, set-abstraction blocks, one
 2B feedback pass); `composed`: the same mirrors grouping / attending / convolving the way the
 reference composes them in PyTorch over the nine drop-in operators, two feedback passes.
 Also times the classifier training step (`train_one_epoch`, :471-512) with its resampler.
-Prints one JSON line per configuration.
+`--hoisted` (fused mode): the step three times in one process -- today's feature-propagation decoders, the hoisted ones
+(adaptpoint_amd.propagation), today's again: the repeated leg shows the spread a difference has to exceed.
+Prints one JSON line per configuration (`--out FILE` appends them there as well).
 """
 import argparse
 import json
@@ -56,6 +58,9 @@ def main():
     ap.add_argument("--stamps", action="store_true",
                     help="capture device wall-clock stamps at the step's phase boundaries (adaptpoint_amd.graphs."
                          "PhaseStamps) and print them after the run")
+    ap.add_argument("--hoisted", action="store_true",
+                    help="fused mode: also time the step with the generator's decoders hoisted (plain, hoisted, plain)")
+    ap.add_argument("--out", default="", help="append the JSON lines to this file")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
@@ -63,10 +68,13 @@ def main():
     pos = torch.from_numpy(GI.unit_sphere_cloud(a.batch, a.points, seed=0))
     points = torch.cat([pos, pos[:, :, 1:2] - pos[:, :, 1:2].min(1, keepdim=True)[0]], -1).to(dev)
     label = (torch.arange(a.batch) % 15).to(dev)
+    legs = []
     for mode in (("fused", "composed") if a.mode == "both" else (a.mode,)):
+        legs += [(mode, h) for h in ((False, True, False) if (a.hoisted and mode == "fused") else (False,))]
+    for mode, hoisted in legs:
         fused = mode == "fused"
         torch.manual_seed(0)
-        G = AdaptPointAugmentor(fused=fused).to(dev)
+        G = AdaptPointAugmentor(fused=fused, hoisted=hoisted).to(dev)
         D = PointDiscriminator1(num_classes=15, fused=fused).to(dev)
         C = PointNextSClassifier(fused=fused).to(dev)
         step = GanStep(G, D, C, SmoothCrossEntropy(0.3), batched_feedback=fused, capturable=a.graph,
@@ -93,6 +101,8 @@ def main():
                "ms_per_step": round(sec * 1e3, 3), "clouds_per_s": round(a.batch / sec, 1),
                "peak_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
                "launch": "hipGraph replay" if a.graph else "eager", "overlap": bool(a.overlap and fused)}
+        if a.hoisted:
+            res["hoisted"] = hoisted
         if a.graph:
             # host time of a replay call alone (hipGraphLaunch enqueues the nodes one by one on this stack: a step
             # of ~900 nodes can be bound by the enqueue, not by the device)
@@ -104,6 +114,9 @@ def main():
         out = captured if a.graph else step(points, label)
         res["losses"] = {k: round(float(out[k]), 5) for k in ("g_loss_raw", "feedback_loss", "d_loss")}
         print(json.dumps(res), flush=True)
+        if a.out:
+            with open(a.out, "a") as fh:
+                fh.write(json.dumps(res) + "\n")
         if a.graph and a.stamps:
             prev = 0.0
             for name, us in apn_graphs.STAMPS.report():
