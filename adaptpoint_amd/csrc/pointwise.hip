@@ -667,7 +667,8 @@ __global__ __launch_bounds__(256) void pw_bn_act_kernel(int B, int C, int N, con
         stat[2 * C + c] = sc;
         stat[3 * C + c] = sh;
     }
-    const bool vec = (N & 3) == 0;
+    // float4 access needs 16-byte aligned rows: N a multiple of 4 AND aligned origins (a contiguous view may start at any float)
+    const bool vec = (N & 3) == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     pw_for_rows(B, N, C, c, [&](size_t off) {
         if (vec) {
             const float4 *src = reinterpret_cast<const float4 *>(y + off);
@@ -741,7 +742,8 @@ __global__ __launch_bounds__(256) void pw_bwd_apply_kernel(int B, int C, int N, 
         k1 = (float)(-(double)sc * (double)inv * m2);
         k0 = (float)(-(double)sc * m1 + (double)sc * (double)inv * m2 * (double)mean);
     }
-    const bool vec = (N & 3) == 0;
+    const bool vec = (N & 3) == 0 &&           // (and aligned origins: pw_bn_act_kernel)
+                     ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0;
     pw_for_rows(B, N, C, c, [&](size_t off) {
         if (vec) {
             const float4 *gs = reinterpret_cast<const float4 *>(g + off), *ys = reinterpret_cast<const float4 *>(y + off);
@@ -1214,7 +1216,7 @@ extern "C" int apn_pw_contract(int nbatch, int r, int q, int k, const float *a, 
                                int ldd, int splits, float *scratch, int precision, void *stream) {
     using namespace apn;
     if (nbatch <= 0 || r <= 0 || q <= 0 || k <= 0 || nbatch > 65535 || !a || !b || !d || (precision != 2 && precision != 3) ||
-        splits < 0 || (splits > 0 && (!scratch || ldd != q)))
+        splits < 0 || ldd < q || (splits > 0 && (!scratch || ldd != q)))
         return APN_EINVAL;
     PwGemm g{};
     g.A = PwOperand{a, a_batch, lda};

@@ -603,7 +603,7 @@ APN_API int apn_pw_conv_grad_weight(int b, int c_in, int c_out, int n, int preci
 
 /* The contraction kernel of the per-point layers as such (csrc/pointwise.hip), for the small dense products around
  * the fused set-abstraction blocks (conv1 at the points, dL/df, dL/dW1 of the wide blocks):
- *   splits == 0: d[z] (r x q) = a[z] (r x k) b[z] (k x q), z < nbatch (a batch stride of 0 shares the operand);
+ *   splits == 0: d[z] (r x q, ldd >= q) = a[z] (r x k) b[z] (k x q), z < nbatch (a batch stride of 0 shares the operand);
  *   splits  > 0: d (r x q, ldd == q) = sum_z a[z] b[z] in `splits` shares (apn_pw_contract_splits; scratch
  *                [splits][r][q]) added in a fixed order.
  * a_kcont / b_kcont: the operand's element (i, k) lies at i * ld + k (1) or at k * ld + i (0). */

@@ -129,6 +129,33 @@ def test_argument_validation_of_the_adaptpoint_entries_needs_no_gpu():
     assert lib.apn_pw_conv_grad_weight(2, 8, 8, 16, 3, None, None, None, None, None) == EINVAL
     assert lib.apn_pw_conv_max_backward(2, 129, 8, 16, None, None, None, None, None, 1, None, None, None, None, None) == EINVAL
     assert lib.apn_pw_contract(1, 4, 4, 4, None, 0, 4, 1, None, 0, 4, 1, None, 0, 4, 0, None, 3, None) == EINVAL
+    # the raw contraction entries: every check returns before any launch (P: a non-null address that is never read)
+    P = 4096
+    contract = lambda nbatch=1, ldd=4, splits=0, scratch=None, precision=3, a=P, b=P, d=P: lib.apn_pw_contract(
+        nbatch, 4, 4, 4, a, 0, 4, 1, b, 0, 4, 1, d, 0, ldd, splits, scratch, precision, None)
+    assert contract(ldd=3) == EINVAL                                   # ldd < q
+    assert contract(ldd=5, splits=2, scratch=P) == EINVAL              # the split form writes a tight result
+    assert contract(splits=2) == EINVAL                                # ... and needs its scratch
+    assert contract(splits=-1) == EINVAL
+    assert contract(precision=4) == EINVAL and contract(precision=1) == EINVAL
+    assert contract(nbatch=65536) == EINVAL and contract(nbatch=0) == EINVAL
+    assert contract(a=None) == EINVAL and contract(b=None) == EINVAL and contract(d=None) == EINVAL
+    I2, L2, P2 = ctypes.c_int * 2, ctypes.c_longlong * 2, ctypes.c_void_p * 2
+
+    def contract2(nbatch=(1, 1), ldd=(4, 4), splits=(0, 0), scratch=(None, None), precision=3, null=None, a=(P, P)):
+        args = [I2(*nbatch), I2(4, 4), I2(4, 4), I2(4, 4), P2(*a), L2(0, 0), I2(4, 4), P2(P, P), L2(0, 0), I2(4, 4), P2(P, P),
+                L2(0, 0), I2(*ldd), I2(*splits), P2(*scratch)]
+        if null is not None:
+            args[null] = None
+        return lib.apn_pw_contract2(1, 1, precision, *args, None)
+    assert contract2(ldd=(4, 3)) == EINVAL and contract2(ldd=(3, 4)) == EINVAL                 # ldd < q
+    assert contract2(splits=(2, 0), scratch=(P, P)) == EINVAL and contract2(splits=(0, 2), scratch=(P, P)) == EINVAL   # both or neither
+    assert contract2(splits=(2, 2), scratch=(P, None)) == EINVAL
+    assert contract2(precision=4) == EINVAL
+    assert contract2(nbatch=(1, 65536)) == EINVAL and contract2(nbatch=(0, 1)) == EINVAL
+    assert contract2(a=(P, None)) == EINVAL
+    for i in range(15):
+        assert contract2(null=i) == EINVAL, i                          # a null array
     # split-K shares: short contractions down to two chunks per share, long ones at least eight, <= 256 workgroups (one per CU)
     assert lib.apn_pw_contract_splits(1, 256, 256, 512) == 8 and lib.apn_pw_contract_splits(32, 512, 1536, 256) == 5
     assert lib.apn_spectral_norm(0, 4, None, 1, 1e-12, None, None, None, None, None, None, None, None) == EINVAL
