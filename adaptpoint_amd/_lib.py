@@ -154,6 +154,10 @@ SIGNATURES = {
     "apn_rsmix_mix": [_c_int] * 4 + [_c_void_p] * 8,
     "apn_cloud_transform": [_c_int] * 4 + [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 8,
     "apn_cls_confusion": [_c_int] * 2 + [_c_void_p, _c_int] + [_c_void_p] * 5,
+    "apn_la_pool_rows": [_c_int] * 2,
+    "apn_la_pool_fwd": [_c_int] * 4 + [_c_float] + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 7,
+    "apn_la_stats_fold": [_c_void_p, _c_int, _c_int, _c_double, _c_void_p, _c_void_p],
+    "apn_la_pool_bwd": [_c_int] * 4 + [_c_float] + [_c_void_p] * 11 + [_c_int] + [_c_void_p] * 4,
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""PointNeXt-S classifier over the gfx950 set-abstraction blocks.
+"""PointNeXt-S classifier over the gfx950 set-abstraction blocks; InvResMLP and the general encoder (B / L / XL).
 
 Host-side mirror of the model `cfgs/scanobjectnn/pointnext-s.yaml:5-36` builds in the reference:
 `BaseCls` (openpoints/models/classification/cls_base.py:13-39) = `PointNextEncoder`
@@ -7,6 +7,11 @@ SetAbstraction and no InvResMLP exists) + `ClsHead` (cls_base.py:78-136).  Modul
 names match the reference (`encoder.encoder.<stage>.0....`, `prediction.head.<i>....`), so a
 reference state_dict loads unchanged.  Stage 1 (1024 -> 512 points, 32 -> 64 channels) has the
 shape the fused kernels cover; the other stages run the unfused extension operators + PyTorch.
+
+`LocalAggregation`, `InvResMLP` (pointnext.py:27-78, 229-276) and `PointNextEncoder` (pointnext.py:311-456, any
+`blocks`) are the depth-scaled models' parts: an InvResMLP's aggregation runs on csrc/local_aggr.hip when fused
+(adaptpoint_amd.local_aggr), its pointwise convolutions on csrc/pointwise.hip, and one ball query + NeighbourIndex
+serves all the InvResMLP blocks of a stage that share radius and nsample.
 """
 import torch
 import torch.nn as nn
@@ -109,6 +114,226 @@ class PointNextEncoderS(nn.Module):
                 torch.cuda.current_stream(p0.device).wait_event(smp.ready)
             p0, f0 = stage[0]([p0, f0], sampling=smp) if smp is not None else stage[0]([p0, f0])
         return f0.squeeze(-1)
+
+
+_BALL = {'NAME': 'ballquery', 'normalize_dp': True}
+
+
+class LocalAggregation(nn.Module):
+    """pointnext.py:27-78: p grouped around p itself, Conv2d-BN-ReLU blocks, a reduction over the neighbours.
+    `forward(pf, index=None)`: index = the neighbours computed ahead -- an idx (B,N,K) tensor or, for the fused
+    kernels, the `fused_wide.NeighbourIndex` of it (one per stage: `PointNextEncoder.stage_index`)."""
+
+    def __init__(self, channels, norm_args=None, act_args=None, group_args=None, conv_args=None, feature_type='dp_fj',
+                 reduction='max', last_act=True, fused=False, sync_bn=False):
+        super().__init__()
+        from .set_abstraction import convblock
+        norm_args = {'norm': 'bn1d'} if norm_args is None else norm_args
+        group_args = dict(group_args or {'NAME': 'ballquery', 'radius': 0.1, 'nsample': 16})
+        if feature_type != 'dp_fj' or reduction.lower() != 'max' or group_args.get('NAME', 'ballquery') != 'ballquery':
+            raise NotImplementedError("only the 'dp_fj' aggregation with a max over ball-query neighbours is on the "
+                                      "hot path")
+        channels = list(channels)
+        channels[0] += 3
+        self.convs = nn.Sequential(*[
+            convblock(channels[i], channels[i + 1], 2, norm_args=norm_args,
+                      act_args=None if i == len(channels) - 2 and not last_act else act_args, **dict(conv_args or {}))
+            for i in range(len(channels) - 1)])
+        from .layers import make_grouper
+        self.grouper = make_grouper(group_args)
+        self.reduction, self.feature_type = 'max', feature_type
+        self.fused, self.sync_bn = fused, sync_bn
+
+    def _uncovered(self, p, f):
+        """None when csrc/local_aggr.hip covers this call, else the reason it does not."""
+        from . import local_aggr
+        blocks = [tuple(b) for b in self.convs]
+        g = self.grouper
+        ok = (len(blocks) == 1 and len(blocks[0]) in (2, 3) and isinstance(blocks[0][1], nn.BatchNorm2d)
+              and (len(blocks[0]) == 2 or isinstance(blocks[0][2], nn.ReLU)))
+        if ok:
+            conv, bn = blocks[0][0], blocks[0][1]
+            ok = (bn.training or bn.track_running_stats) and local_aggr.covers(
+                p.shape[0], p.shape[1], g.nsample, f.shape[1], tuple(conv.weight.shape[:2]), conv.bias is not None,
+                bn.momentum)
+        if ok:
+            return None
+        return (f"LocalAggregation C_in={f.shape[1]} -> {[b[0].out_channels for b in blocks]}, K={g.nsample}: "
+                "no fused kernel for this shape")
+
+    def forward(self, pf, index=None):
+        from . import fused_wide, local_aggr
+        from .set_abstraction import _note_fallback, _ranks
+        p, f = pf
+        g = self.grouper
+        if self.fused and f.is_cuda and f.dtype == torch.float32 and p.dtype == torch.float32:
+            reason = self._uncovered(p, f)
+            if reason is None:
+                if not isinstance(index, fused_wide.NeighbourIndex):
+                    pd = p.detach().contiguous()
+                    idx = index if index is not None else g.neighbours(pd, pd)
+                    index = fused_wide.neighbour_index(idx.contiguous(), pd, p.shape[1])
+                blk = tuple(self.convs[0])
+                return local_aggr.aggregate(p, f, index, g.radius if g.normalize_dp else 1.0, blk[0], blk[1],
+                                            relu=len(blk) == 3, sync_bn=self.sync_bn)
+            if self.sync_bn and _ranks() > 1:
+                raise RuntimeError("LocalAggregation(fused=True, sync_bn=True) cannot run its fused kernels (" + reason +
+                                   ") and its BatchNorm modules are plain ones: convert them "
+                                   "(adaptpoint_amd.dp.convert_sync_batchnorm) or build the block with fused=False")
+            _note_fallback(reason)
+        idx = index.idx if isinstance(index, fused_wide.NeighbourIndex) else index
+        dp, fj = g(p, p, f, idx) if idx is not None else g(p, p, f)
+        return torch.max(self.convs(torch.cat([dp, fj], 1)), dim=-1, keepdim=False)[0]
+
+
+class InvResMLP(nn.Module):
+    """pointnext.py:229-276: LocalAggregation (one grouped convolution), pointwise convolutions with an expansion,
+    the residual add and the activation.  Sub-module names are the reference's (`convs.convs.0.*`, `pwconv.<i>.*`)."""
+
+    def __init__(self, in_channels, norm_args=None, act_args=None, aggr_args=None, group_args=None, conv_args=None,
+                 expansion=1, use_res=True, num_posconvs=2, less_act=False, fused=False, sync_bn=False):
+        super().__init__()
+        from .set_abstraction import _act, convblock
+        norm_args = {'norm': 'bn'} if norm_args is None else norm_args
+        act_args = {'act': 'relu'} if act_args is None else act_args
+        aggr_args = {'feature_type': 'dp_fj', 'reduction': 'max'} if aggr_args is None else aggr_args
+        group_args = dict(_BALL, radius=0.1, nsample=32) if group_args is None else group_args
+        self.use_res, self.fused = use_res, fused
+        mid = int(in_channels * expansion)
+        self.convs = LocalAggregation([in_channels, in_channels], norm_args=norm_args,
+                                      act_args=act_args if num_posconvs > 0 else None, group_args=group_args,
+                                      conv_args=conv_args, fused=fused, sync_bn=sync_bn, **aggr_args)
+        channels = [] if num_posconvs < 1 else ([in_channels, in_channels] if num_posconvs == 1
+                                                else [in_channels, mid, in_channels])
+        self.pwconv = nn.Sequential(*[
+            convblock(channels[i], channels[i + 1], 1, norm_args=norm_args,
+                      act_args=act_args if i != len(channels) - 2 and not less_act else None, **dict(conv_args or {}))
+            for i in range(len(channels) - 1)])
+        self.act = _act(act_args)
+
+    def forward(self, pf, index=None):
+        from . import pointwise
+        p, f = pf
+        identity = f
+        f = self.convs([p, f], index=index)
+        for blk in self.pwconv:
+            f = pointwise.run_block(f, blk, self.fused)
+        if f.shape[-1] == identity.shape[-1] and self.use_res:
+            f = f + identity
+        return [p, self.act(f)]
+
+
+class PointNextEncoder(nn.Module):
+    """pointnext.py:311-456 for any `blocks`: stage i = one SetAbstraction (the stem when i == 0 and its stride is 1)
+    followed by blocks[i] - 1 InvResMLP blocks; nesting `encoder.<stage>.<j>`, so a reference state_dict loads
+    unchanged.  group_args: the grouper's settings besides radius and nsample (the cfgs set normalize_dp)."""
+
+    def __init__(self, in_channels=4, width=32, blocks=(1, 4, 7, 4, 4), strides=(4, 4, 4, 4), block='InvResMLP',
+                 nsample=32, radius=0.1, radius_scaling=2, nsample_scaling=1, sa_layers=1, sa_use_res=False,
+                 expansion=4, use_res=True, aggr_args=None, group_args=None, norm_args=None, act_args=None,
+                 conv_args=None, sampler='fps', fused=False, sync_bn=False):
+        super().__init__()
+        if block not in ('InvResMLP', InvResMLP):
+            raise NotImplementedError(f"block '{block}' is outside the hot-path build")
+        self.blocks, self.strides = list(blocks), list(strides)
+        self.fused, self.sync_bn = fused, sync_bn
+        aggr_args = {'feature_type': 'dp_fj', 'reduction': 'max'} if aggr_args is None else dict(aggr_args)
+        base = dict(_BALL if group_args is None else group_args)
+        norm_args = {'norm': 'bn'} if norm_args is None else norm_args
+        act_args = {'act': 'relu'} if act_args is None else act_args
+        self.radii = self._to_full_list(radius, radius_scaling)
+        self.nsample = self._to_full_list(nsample, nsample_scaling)
+        channels = []
+        for s in self.strides:
+            if s != 1:
+                width *= 2
+            channels.append(width)
+        stages, cin = [], in_channels
+        for i, nblk in enumerate(self.blocks):
+            is_head = i == 0 and self.strides[i] == 1
+            radii, ns = self.radii[i], self.nsample[i]
+            layers = [SetAbstraction(cin, channels[i], layers=sa_layers if not is_head else 1, stride=self.strides[i],
+                                     group_args=dict(base, radius=radii[0], nsample=ns[0]), sampler=sampler,
+                                     norm_args=norm_args, act_args=act_args, conv_args=conv_args, is_head=is_head,
+                                     use_res=sa_use_res, feature_type=aggr_args['feature_type'], fused=fused,
+                                     sync_bn=sync_bn)]
+            cin = channels[i]
+            for j in range(1, nblk):
+                layers.append(InvResMLP(cin, aggr_args=aggr_args, norm_args=norm_args, act_args=act_args,
+                                        group_args=dict(base, radius=radii[j], nsample=ns[j]), conv_args=conv_args,
+                                        expansion=expansion, use_res=use_res, fused=fused, sync_bn=sync_bn))
+            stages.append(nn.Sequential(*layers))
+        self.encoder = nn.Sequential(*stages)
+        self.out_channels = channels[-1]
+        self.channel_list = channels
+
+    def _to_full_list(self, param, param_scaling=1):
+        """pointnext.py:389-407: one value per block of every stage, from a scalar (grown after every down-sampling
+        stage, its later blocks already at the grown value) or from a (nested) list padded with its last entry."""
+        full = []
+        if isinstance(param, (list, tuple)):
+            for i, value in enumerate(param):
+                value = list(value) if isinstance(value, (list, tuple)) else [value]
+                full.append(value + [value[-1]] * (self.blocks[i] - len(value)))
+        else:
+            for i, s in enumerate(self.strides):
+                if s == 1:
+                    full.append([param] * self.blocks[i])
+                else:
+                    full.append([param] + [param * param_scaling] * (self.blocks[i] - 1))
+                    param *= param_scaling
+        return full
+
+    @torch.no_grad()
+    def stage_index(self, stage, p):
+        """The index work of a stage's InvResMLP blocks for its points p (B,N,3) -- coordinates only, so it belongs
+        with the index pyramid: ONE ball query of p around p per distinct (radius, nsample) among the blocks and,
+        where the fused kernels will consume it, ONE NeighbourIndex.  -> a list, entry j - 1 for block j."""
+        from . import fused_wide, layers
+        made, res = {}, []
+        p = p.detach().contiguous()
+        for blk in list(stage)[1:]:
+            la = blk.convs
+            g = la.grouper
+            key = (g.radius, g.nsample)
+            if key not in made:
+                idx = layers.ball_query(g.radius, g.nsample, p, p)
+                if la.fused and p.is_cuda and p.dtype == torch.float32 and g.nsample == 32:
+                    idx = fused_wide.neighbour_index(idx, p, p.shape[1])
+                made[key] = idx
+            res.append(made[key])
+        return res
+
+    def _stage(self, stage, p, f):
+        p, f = stage[0]([p, f])
+        if len(stage) > 1:
+            for blk, index in zip(list(stage)[1:], self.stage_index(stage, p)):
+                p, f = blk([p, f], index=index)
+        return p, f
+
+    def forward_cls_feat(self, p0, f0=None):
+        if hasattr(p0, 'keys'):
+            p0, f0 = p0['pos'], p0.get('x', None)
+        if f0 is None:
+            f0 = p0.clone().transpose(1, 2).contiguous()
+        for stage in self.encoder:
+            p0, f0 = self._stage(stage, p0, f0)
+        return f0.squeeze(-1)
+
+    def forward_seg_feat(self, p0, f0=None):
+        if hasattr(p0, 'keys'):
+            p0, f0 = p0['pos'], p0.get('x', None)
+        if f0 is None:
+            f0 = p0.clone().transpose(1, 2).contiguous()
+        p, f = [p0], [f0]
+        for stage in self.encoder:
+            _p, _f = self._stage(stage, p[-1], f[-1])
+            p.append(_p)
+            f.append(_f)
+        return p, f
+
+    def forward(self, p0, f0=None):
+        return self.forward_seg_feat(p0, f0)
 
 
 class FeaturePropagation(nn.Module):

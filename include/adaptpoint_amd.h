@@ -776,6 +776,29 @@ APN_API int apn_spectral_norm_grad_many(int n_layers, const int *rows, const int
                                         const float *const *u_used, const float *const *v_used, double *const *part,
                                         float *const *g_w, void *stream);
 
+/* LocalAggregation with one grouped convolution (InvResMLP's aggregation, pointnext.py:27-78, 246), the feature part of
+ * the convolution hoisted to the points: U (b,n,c) = Wf f, y[q,k] = U[idx[q,k]] + Wp (xyz[idx[q,k]] - xyz[q]) / radius
+ * (csrc/local_aggr.hip).  c in {64, 128, 256, 512}, nsample = 32, idx (b,n,32) a ball query of xyz (b,n,3) around itself,
+ * wp: the convolution's coordinate columns (c rows of stride ldw).
+ *   pool_fwd: ext (b,n,c) = ext_k y[q,k] (max where gamma >= 0, min elsewhere; gamma NULL: max), sel (b,n,c) uint8 = the
+ *     slot that holds it; training (ysum and part both given): ysum (b,n,c) = sum_k y[q,k] and
+ *     part[apn_la_pool_rows(b, n)][2c] (float64) = the workgroups' shares of {sum y, sum y^2} over the b*n*32 positions.
+ *   stats_fold: sums[2c + 2] (float64) = {the shares added in a fixed order, count, 1}: apn_sa_bn_fold's `sums`.
+ *   pool_bwd: gsel (b,n,c) = the gradient at the selected positions (apn_sa_wide_bwd_prep's goa), de = {D[c], E[c]}
+ *     (apn_sa_wide_consts2: BatchNorm's dense term dL/dy = D y + E), tmap / pcnt_poff / plist / geo: the NeighbourIndex
+ *     of idx (apn_sa_wide_tilemap, apn_sa_wide_csr) -> dU (b,n,c) = dL/dU summed per point in a fixed order (no float
+ *     atomics), dT (b,n,c) = dU - sum_k dL/dy[n,k] (dL/dWp = dT^T xyz / radius) and (dp given) dp (b,n,3) =
+ *     dT wp / radius.  ysum NULL: eval mode (D = E = 0). */
+APN_API int apn_la_pool_rows(int b, int n);
+APN_API int apn_la_pool_fwd(int b, int n, int c, int nsample, float radius, const float *U, const float *xyz,
+                            const float *wp, int ldw, const int *idx, const float *gamma, float *ext, void *sel,
+                            float *ysum, double *part, void *stream);
+APN_API int apn_la_stats_fold(const double *part, int rows, int c, double count, double *sums, void *stream);
+APN_API int apn_la_pool_bwd(int b, int n, int c, int nsample, float radius, const float *gsel, const void *sel,
+                            const int *tmap, const int *pcnt_poff, const int *plist, const float *geo, const float *U,
+                            const float *xyz, const float *ysum, const float *de, const float *wp, int ldw, float *dU,
+                            float *dT, float *dp, void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
