@@ -20,9 +20,24 @@ HEAD_DIM = 16
 COMPOSED_CALLS = {}
 
 
+MAX_GRID = 65535     # clouds and heads are grid dimensions y / z of every kernel (attn_check)
+
+
 def supported(q, heads):
     return (q.is_cuda and q.dim() == 3 and q.shape[-1] == heads * HEAD_DIM and q.shape[1] % 32 == 0
-            and q.shape[1] > 0)
+            and q.shape[1] > 0 and 0 < q.shape[0] <= MAX_GRID and 0 < heads <= MAX_GRID)
+
+
+def _why_composed(q, heads):
+    if heads <= 0:
+        return "heads %d" % heads
+    if q.dim() != 3 or q.shape[-1] != heads * HEAD_DIM:
+        return "head dim %d" % (q.shape[-1] // heads)
+    if q.shape[0] > MAX_GRID:
+        return "batch %d above %d" % (q.shape[0], MAX_GRID)
+    if heads > MAX_GRID:
+        return "heads %d above %d" % (heads, MAX_GRID)
+    return "M=%d not a multiple of 32" % q.shape[1]
 
 
 def _reference(q, k, v, heads):
@@ -101,10 +116,10 @@ def attention(q, k, v, heads):
                            "CPU fallback")
     _lib.load()
     if (q.dim() == 3 and q.shape[-1] == heads * HEAD_DIM and 0 < q.shape[1] <= SMALL_MAX and q.shape[1] % 32
-            and 0 < q.shape[0] <= 65535):
+            and 0 < q.shape[0] <= MAX_GRID and 0 < heads <= MAX_GRID):
         return _AttentionSmall.apply(q, k, v, heads)   # few points (the 4-anchor head): one wave per (cloud, head)
     if not supported(q, heads):                      # other head dims / ragged M > 32: composed on the GPU, and counted
-        why = "M=%d not a multiple of 32" % q.shape[1] if q.shape[-1] == heads * HEAD_DIM else "head dim %d" % (q.shape[-1] // heads)
+        why = _why_composed(q, heads)
         COMPOSED_CALLS[why] = COMPOSED_CALLS.get(why, 0) + 1
         return _reference(q, k, v, heads)
     return _Attention.apply(q, k, v, heads)

@@ -338,6 +338,9 @@ static int attn_check(int b, int m, int heads) {
     return APN_OK;
 }
 
+// out, dq, dk, dv are written as float4, the images and the scratch read as uint4 / written as bf16x8
+static bool attn_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace apn
 
 // Operand images: six of b*heads*m*32 bf16 (64 bytes per point and head) each, in `images`:
@@ -498,7 +501,7 @@ extern "C" int apn_attention_prep(int b, int m, int heads, const float *q, const
                                   const float *v, void *images, int for_backward, void *stream) {
     using namespace apn;
     if (int e = attn_check(b, m, heads)) return e;
-    if (!q || !k || !v || !images) return APN_EINVAL;
+    if (!q || !k || !v || !images || !attn_aligned16(images)) return APN_EINVAL;
     const size_t n = (size_t)b * heads * m * 32;
     __bf16 *im = (__bf16 *)images;
     const dim3 grid(m / 32, heads, b);
@@ -518,7 +521,7 @@ extern "C" int apn_attention_fwd(int b, int m, int heads, const void *images, fl
                                  void *stream) {
     using namespace apn;
     if (int e = attn_check(b, m, heads)) return e;
-    if (!images || !out || !lse) return APN_EINVAL;
+    if (!images || !out || !lse || !attn_aligned16(images) || !attn_aligned16(out)) return APN_EINVAL;
     const size_t n = (size_t)b * heads * m * 32;
     const __bf16 *im = (const __bf16 *)images;
     const int per_wg = AT_WAVES * 32;
@@ -530,12 +533,16 @@ extern "C" int apn_attention_fwd(int b, int m, int heads, const void *images, fl
 
 // g_out (B,M,H*16) = dL/d out; out, lse from the forward; images from apn_attention_prep(...,
 // for_backward = 1); scratch: 2 * b*heads*m*32 bf16 (images of g_out) + b*heads*m floats (delta).
+// images, scratch, dq, dk, dv (and the forward's out) must be 16-byte aligned: APN_EINVAL otherwise.
 extern "C" int apn_attention_bwd(int b, int m, int heads, const void *images, const float *out,
                                  const float *lse, const float *g_out, void *scratch, float *dq,
                                  float *dk, float *dv, void *stream) {
     using namespace apn;
     if (int e = attn_check(b, m, heads)) return e;
     if (!images || !out || !lse || !g_out || !scratch || !dq || !dk || !dv) return APN_EINVAL;
+    if (!attn_aligned16(images) || !attn_aligned16(scratch) || !attn_aligned16(dq) || !attn_aligned16(dk) ||
+        !attn_aligned16(dv))
+        return APN_EINVAL;
     const size_t n = (size_t)b * heads * m * 32;
     const __bf16 *im = (const __bf16 *)images;
     __bf16 *gs = (__bf16 *)scratch, *gt = gs + n;

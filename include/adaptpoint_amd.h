@@ -396,6 +396,8 @@ APN_API int apn_pointset_group_max_grad(int b, int n, int m, int c, int k, const
  * apn_attention_fwd also returns lse (B,heads,M), the log2-domain log-sum-exp of every query.
  * apn_attention_bwd: g_out = dL/d out -> dq, dk, dv (B,M,heads*16); scratch = 2 * b*heads*m*32
  * bf16 + b*heads*m floats.
+ * b, heads <= 65535 (grid dimensions).  `images`, `scratch`, `out`, dq, dk, dv are reached by 16-byte vector accesses
+ * and must be 16-byte aligned (the row pitch heads*64 bytes keeps every row so): APN_EINVAL otherwise, before any launch.
  * ------------------------------------------------------------------------ */
 /* The same attention for few points (0 < m <= apn_attention_small_max() = 32; the imitator's 4-anchor head): one wave
  * per (cloud, head) in float32; the backward recomputes the probabilities from q, k, v. */

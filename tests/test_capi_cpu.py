@@ -165,3 +165,46 @@ def test_argument_validation_of_the_adaptpoint_entries_needs_no_gpu():
     assert lib.apn_deform_forward(2, 5000, 4, None, None, None, None, None, None, 0.5, None, None, None, None) == EINVAL   # n <= 4096
     assert lib.apn_deform_forward(2, 1024, 9, None, None, None, None, None, None, 0.5, None, None, None, None) == EINVAL   # m <= 8
     assert lib.apn_deform_forward(0, 1024, 4, None, None, None, None, None, None, 0.5, None, None, None, None) == 0
+
+
+def test_argument_validation_of_the_attention_entries_needs_no_gpu():
+    """The five apn_attention_* entries reject null pointers, m = 0, an m the kernel has no tile for, b / heads of 0 or
+    above 65535 (grid dimensions) and pointers that their 16-byte vector accesses could not take -- all before any launch
+    (P: a non-null, 16-byte aligned address that is never read)."""
+    from adaptpoint_amd import _lib
+    lib = _lib.load()
+    EINVAL, P = -1, 4096
+    assert lib.apn_attention_small_max() == 32
+
+    def prep(b=1, m=32, heads=1, q=P, k=P, v=P, images=P, for_backward=1):
+        return lib.apn_attention_prep(b, m, heads, q, k, v, images, for_backward, None)
+
+    def fwd(b=1, m=32, heads=1, images=P, out=P, lse=P):
+        return lib.apn_attention_fwd(b, m, heads, images, out, lse, None)
+
+    def bwd(b=1, m=32, heads=1, images=P, out=P, lse=P, g_out=P, scratch=P, dq=P, dk=P, dv=P):
+        return lib.apn_attention_bwd(b, m, heads, images, out, lse, g_out, scratch, dq, dk, dv, None)
+
+    def small_fwd(b=1, m=4, heads=1, q=P, k=P, v=P, out=P):
+        return lib.apn_attention_small_fwd(b, m, heads, q, k, v, out, None)
+
+    def small_bwd(b=1, m=4, heads=1, q=P, k=P, v=P, g_out=P, dq=P, dk=P, dv=P):
+        return lib.apn_attention_small_bwd(b, m, heads, q, k, v, g_out, dq, dk, dv, None)
+
+    pointers = {prep: ["q", "k", "v", "images"], fwd: ["images", "out", "lse"],
+                bwd: ["images", "out", "lse", "g_out", "scratch", "dq", "dk", "dv"], small_fwd: ["q", "k", "v", "out"],
+                small_bwd: ["q", "k", "v", "g_out", "dq", "dk", "dv"]}
+    for entry, names in pointers.items():
+        for name in names:
+            assert entry(**{name: None}) == EINVAL, (entry.__name__, name)
+        assert entry(m=0) == EINVAL and entry(m=-32) == EINVAL and entry(m=33) == EINVAL, entry.__name__
+        for bad in (0, -1, 65536):
+            assert entry(b=bad) == EINVAL and entry(heads=bad) == EINVAL, (entry.__name__, bad)
+    for entry in (prep, fwd, bwd):
+        assert entry(m=16) == EINVAL and entry(m=48) == EINVAL                     # whole 32-tiles only
+    # float4 / uint4 / bf16x8 accesses: 16-byte alignment of what they reach
+    aligned = {prep: ["images"], fwd: ["images", "out"], bwd: ["images", "scratch", "dq", "dk", "dv"]}
+    for entry, names in aligned.items():
+        for name in names:
+            for off in (2, 4, 8):
+                assert entry(**{name: P + off}) == EINVAL, (entry.__name__, name, off)
