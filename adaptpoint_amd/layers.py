@@ -99,6 +99,41 @@ def three_nn(unknown, known):
     return d2.sqrt_(), nearest
 
 
+KNN_MAX_K, KNN_MAX_C = 64, 128
+
+
+def knn_covers(support, query, k):
+    """Whether `knn_query` takes these tensors: CUDA float32 (B,N,C) / (B,M,C) within the kernel's limits."""
+    if not (support.is_cuda and query.is_cuda and support.dtype == torch.float32 and query.dtype == torch.float32
+            and support.dim() == 3 and query.dim() == 3 and support.shape[0] == query.shape[0]
+            and support.shape[2] == query.shape[2]):
+        return False
+    B, N, C = support.shape
+    return (1 <= k <= min(KNN_MAX_K, N) and 1 <= C <= KNN_MAX_C and B <= 65535
+            and B * max(N, query.shape[1]) < 2 ** 24)
+
+
+@torch.no_grad()
+def knn_query(support, query, k, return_dist=False):
+    """The k nearest `support` (B,N,C) rows of every `query` (B,M,C) row, exactly (csrc/knn.hip): squared distances by
+    direct differences in float32, the k smallest keys (distance, support index) in ascending order -- ties go to the
+    smaller index.  -> idx (B,M,k) int32 [, dist2 (B,M,k)].  No (B,M,N) tensor exists."""
+    from .fused import _call, _ptr
+    if not (support.is_cuda and query.is_cuda):
+        raise RuntimeError("adaptpoint_amd.layers needs CUDA/HIP tensors: the product path has no CPU fallback")
+    if support.dtype != torch.float32 or query.dtype != torch.float32:
+        raise RuntimeError("knn_query takes float32 tensors")
+    _need_contiguous(support=support, query=query)
+    B, N, C = support.shape
+    M = query.shape[1]
+    if query.shape[0] != B or query.shape[2] != C:
+        raise RuntimeError(f"knn_query: query {tuple(query.shape)} does not match support {tuple(support.shape)}")
+    idx = _alloc(support, B, M, k, dtype=torch.int32)
+    d2 = _alloc(support, B, M, k) if return_dist else None
+    _call("apn_knn_query", support.device, B, N, M, C, k, support.data_ptr(), query.data_ptr(), idx.data_ptr(), _ptr(d2))
+    return (idx, d2) if return_dist else idx
+
+
 # ---------------------------------------------------------------- copy operators (gradient = scatter-add)
 class _TakeRows(Function):
     """out[b, c, ...] = features[b, c, idx[b, ...]] for idx (B,M) ("gather", subsample.py:108-141)
@@ -243,6 +278,8 @@ class KnnGrouper(nn.Module):
 
     @torch.no_grad()
     def neighbours(self, query_xyz, support_xyz):
+        if knn_covers(support_xyz, query_xyz, self.nsample):
+            return knn_query(support_xyz.contiguous(), query_xyz.contiguous(), self.nsample)
         # distances laid out (B,N,M) and the k smallest taken along N, as the reference does: the
         # order among near-equal distances then is the same
         nearest = torch.cdist(support_xyz, query_xyz).topk(self.nsample, dim=1, largest=False).indices

@@ -407,15 +407,17 @@ class PointNextDecoder(nn.Module):
 
 
 class ClsHead(nn.Module):
-    """cls_base.py:78-136 with mlps [512, 256], BatchNorm1d, ReLU, dropout 0.5."""
+    """cls_base.py:78-136 with mlps [512, 256], BatchNorm1d, ReLU, dropout 0.5.  `act`: a callable that makes the
+    hidden layers' activation (None: ReLU)."""
 
-    def __init__(self, num_classes=15, in_channels=512, mlps=(512, 256), dropout=0.5):
+    def __init__(self, num_classes=15, in_channels=512, mlps=(512, 256), dropout=0.5, act=None):
         super().__init__()
+        act = (lambda: nn.ReLU(inplace=True)) if act is None else act
         dims = [in_channels] + list(mlps) + [num_classes]
         heads = []
         for i in range(len(dims) - 2):
             heads.append(nn.Sequential(nn.Linear(dims[i], dims[i + 1], bias=False),
-                                       nn.BatchNorm1d(dims[i + 1]), nn.ReLU(inplace=True)))
+                                       nn.BatchNorm1d(dims[i + 1]), act()))
             if dropout:
                 heads.append(nn.Dropout(dropout))
         heads.append(nn.Sequential(nn.Linear(dims[-2], dims[-1])))

@@ -122,6 +122,9 @@ def _act(act_args):
     name = act_args.get('act', 'relu')
     if name == 'relu':
         return nn.ReLU(inplace=act_args.get('inplace', True))
+    if name == 'leakyrelu':
+        # create_act (layers/activation.py): nn.LeakyReLU(negative_slope, inplace)
+        return nn.LeakyReLU(act_args.get('negative_slope', 0.01), inplace=act_args.get('inplace', True))
     raise NotImplementedError(f"activation '{name}' is outside the hot-path build")
 
 

@@ -801,6 +801,44 @@ APN_API int apn_la_pool_bwd(int b, int n, int c, int nsample, float radius, cons
                             const float *xyz, const float *ysum, const float *de, const float *wp, int ldw, float *dU,
                             float *dT, float *dp, void *stream);
 
+/* Exact brute-force k nearest neighbours of c-dimensional rows (csrc/knn.hip): for every query (b,m,c) the k supports
+ * (b,n,c) with the smallest key (d2, support index), ascending -- ties go to the smaller index --, where
+ * d2 = sum_c (q_c - s_c)^2 in fp32 by direct differences, a_0 = t_0 t_0, a_c = fma(t_c, t_c, a_{c-1}) over ascending c.
+ * idx (b,m,k) int32, dist2 (b,m,k) or NULL; query may alias support.  1 <= k <= 64, k <= n, 1 <= c <= 128, b <= 65535,
+ * b * max(n, m) < 2^24, non-null pointers: APN_EINVAL otherwise, before any HIP call; b == 0 or m == 0 is a no-op.
+ * One launch: no synchronisation, memset or allocation.  Inputs are assumed finite. */
+APN_API int apn_knn_query(int b, int n, int m, int c, int k, const float *support, const float *query, int *idx,
+                          float *dist2, void *stream);
+
+/* DGCNN's EdgeConv block, out = act(bn(max_k W [x_i ; x_j - x_i])) with W = [Wa | Wb] and act = LeakyReLU(slope), the
+ * convolution hoisted to the points (csrc/edge_conv.hip): uv (b,n) rows [u (c) | v (c)] of pitch ld >= 2c (ld % 4 == 0),
+ * u = (Wa - Wb) x, v = Wb x, y[i,k] = u_i + v_idx[i,k].  c in {64, 128, 256, 512}, idx (b,n,k) with 1 <= k <= 64 (indices
+ * outside the cloud are clamped into it), b <= 65535, b * n < 2^24; APN_EINVAL otherwise, before any launch; b == 0 or
+ * n == 0 is a no-op.  No entry synchronises, allocates or issues a memset.
+ *   pool_fwd: ext (b,n,c) = ext_k y[i,k] (max where gamma >= 0, min elsewhere; gamma NULL: max), sel (b,n,c) uint8 = the
+ *     first slot that holds it; training (ysum and part both given): ysum (b,n,c) = sum_k y[i,k] and
+ *     part[apn_ec_pool_rows(b, n)][2c] (float64) = the workgroups' shares of {sum y, sum y^2} over the b*n*k positions
+ *     (repeated neighbours count once per occurrence); apn_la_stats_fold adds them for apn_sa_bn_fold.
+ *   out: out (b,c,n) = act(scale ext + shift), pack = apn_sa_bn_fold's; slope > 0.
+ *   bwd_prep: g (b,c,n; element strides gs_*) -> gsel (b,n,c) = g act' scale and part_s[apn_ec_bwd_prep_rows(b, n)][2c] =
+ *     {sum g act', sum g act' yhat_sel}: apn_sa_wide_consts2's rows.
+ *   csr: the reverse neighbours of idx: pcnt_poff = {pcnt[b n], poff[b n]}, plist[b n k] = the positions (b n + i) k + slot
+ *     that gather each point, ascending -- a pure function of idx; scratch: b n (k + 1) ints.
+ *   pool_bwd: de = {D[c], E[c]} (apn_sa_wide_consts2: BatchNorm's dense term dL/dy = D y + E) -> duv (b,n) rows
+ *     [du | dv] of pitch 2c, du_i = gsel_i + D ysum_i + k E, dv_j = sum over j's list {gsel_i [slot == sel_i]} +
+ *     D (sum over j's list u_i + pcnt_j v_j) + pcnt_j E, summed in list order (no float atomics).  ysum NULL: eval mode. */
+APN_API int apn_ec_pool_rows(int b, int n);
+APN_API int apn_ec_pool_fwd(int b, int n, int c, int k, const float *uv, int ld, const int *idx, const float *gamma,
+                            float *ext, void *sel, float *ysum, double *part, void *stream);
+APN_API int apn_ec_out(int b, int n, int c, const float *ext, const float *pack, float slope, float *out, void *stream);
+APN_API int apn_ec_bwd_prep_rows(int b, int n);
+APN_API int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
+                            const float *ext, const float *pack, float slope, float *gsel, float *part_s, void *stream);
+APN_API int apn_ec_csr(int b, int n, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream);
+APN_API int apn_ec_pool_bwd(int b, int n, int c, int k, const float *gsel, const void *sel, const int *pcnt_poff,
+                            const int *plist, const float *uv, int ld, const float *ysum, const float *de, float *duv,
+                            void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
