@@ -194,9 +194,10 @@ def deform_normalise_mask(x, anchors, lin, off, kernel_axes, mask0, sigma, fused
 
 
 def unit_sphere(z):
-    """Centre each cloud and scale it just inside the unit sphere (:313-327)."""
+    """Centre each cloud and scale it just inside the unit sphere (:313-327).  `.max(dim)[0]`, as the reference: among
+    exactly equal radii the gradient goes to the first point alone, as in csrc/augment.hip (`amax` would split it evenly)."""
     z = z - z.mean(dim=-2, keepdim=True)
-    r = z.square().sum(-1).sqrt().amax(dim=-1)
+    r = z.square().sum(-1).sqrt().max(dim=-1)[0]
     return z * ((1 / r) * 0.999999).view(-1, 1, 1)
 
 

@@ -165,6 +165,31 @@ def test_argument_validation_of_the_adaptpoint_entries_needs_no_gpu():
     assert lib.apn_deform_forward(2, 5000, 4, None, None, None, None, None, None, 0.5, None, None, None, None) == EINVAL   # n <= 4096
     assert lib.apn_deform_forward(2, 1024, 9, None, None, None, None, None, None, 0.5, None, None, None, None) == EINVAL   # m <= 8
     assert lib.apn_deform_forward(0, 1024, 4, None, None, None, None, None, None, 0.5, None, None, None, None) == 0
+    deform_fwd = lambda n=1024, m=4, sigma=0.5: lib.apn_deform_forward(2, n, m, P, P, P, P, P, None, sigma, P, P, P, None)
+    assert deform_fwd(n=4097) == EINVAL and deform_fwd(m=9) == EINVAL and deform_fwd(sigma=0.0) == EINVAL    # the limit alone refuses
+    # the two backward entries: every check returns before a launch (P: a non-null address that is never read)
+
+    def deform_bwd(b=2, n=1024, m=4, sigma=0.5, null=(), mask=P, g_mask=P):
+        ptr = {k: (None if k in null else P) for k in ("xyz", "anchors", "axes", "z", "stat", "g_out", "g_lin", "g_off")}
+        return lib.apn_deform_backward(b, n, m, ptr["xyz"], ptr["anchors"], ptr["axes"], mask, sigma, ptr["z"], ptr["stat"],
+                                       ptr["g_out"], ptr["g_lin"], ptr["g_off"], g_mask, None)
+    everything = ("xyz", "anchors", "axes", "z", "stat", "g_out", "g_lin", "g_off")
+    # the limits, with every pointer non-null: only the limit itself can be what refuses the call
+    assert deform_bwd(n=4097) == EINVAL and deform_bwd(n=0) == EINVAL and deform_bwd(n=-1) == EINVAL           # 0 < n <= 4096
+    assert deform_bwd(m=9) == EINVAL and deform_bwd(m=0) == EINVAL                                             # 0 < m <= 8
+    assert deform_bwd(sigma=0.0) == EINVAL and deform_bwd(sigma=-0.5) == EINVAL                                # sigma > 0
+    assert deform_bwd(b=-1) == EINVAL
+    assert deform_bwd(b=0, null=everything, mask=None, g_mask=None) == 0                                     # no clouds
+    for name in everything:
+        assert deform_bwd(null=(name,)) == EINVAL, name                                                      # required pointers
+
+    def transforms_grad(n=4, null=()):
+        ptr = {k: (None if k in null else P) for k in ("prob", "keep", "axes", "g_prob")}
+        return lib.apn_anchor_transforms_grad(n, ptr["prob"], ptr["keep"], ptr["axes"], 10.0, 3.0, 0.25, P, P, ptr["g_prob"], None)
+    assert transforms_grad(n=-1) == EINVAL                                                                   # all pointers non-null
+    assert transforms_grad(n=0, null=("prob", "keep", "axes", "g_prob")) == 0
+    for name in ("prob", "keep", "axes", "g_prob"):
+        assert transforms_grad(null=(name,)) == EINVAL, name
 
 
 def test_argument_validation_of_the_attention_entries_needs_no_gpu():
