@@ -159,11 +159,14 @@ SIGNATURES = {
     "apn_la_stats_fold": [_c_void_p, _c_int, _c_int, _c_double, _c_void_p, _c_void_p],
     "apn_la_pool_bwd": [_c_int] * 4 + [_c_float] + [_c_void_p] * 11 + [_c_int] + [_c_void_p] * 4,
     "apn_knn_query": [_c_int] * 5 + [_c_void_p] * 5,
+    "apn_knn_dilated": [_c_int] * 7 + [_c_void_p] * 6,
     "apn_ec_pool_rows": [_c_int] * 2,
     "apn_ec_pool_fwd": [_c_int] * 4 + [_c_void_p, _c_int] + [_c_void_p] * 7,
     "apn_ec_out": [_c_int] * 3 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 2,
     "apn_ec_bwd_prep_rows": [_c_int] * 2,
     "apn_ec_bwd_prep": [_c_int] * 3 + [_c_void_p] + [_c_longlong] * 3 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 3,
+    "apn_ec_out_res": [_c_int] * 3 + [_c_void_p] * 2 + [_c_float, _c_void_p] + [_c_longlong] * 3 + [_c_void_p] * 2,
+    "apn_ec_bwd_prep_act": [_c_int] * 3 + [_c_void_p] + [_c_longlong] * 3 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 3,
     "apn_ec_csr": [_c_int] * 3 + [_c_void_p] * 5,
     "apn_ec_pool_bwd": [_c_int] * 4 + [_c_void_p] * 5 + [_c_int] + [_c_void_p] * 4,
 }

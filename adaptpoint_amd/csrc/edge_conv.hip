@@ -1,10 +1,11 @@
 // edge_conv.hip -- the position-level work of a DGCNN EdgeConv block (openpoints/models/layers/graph_conv.py:38-51),
 //
 //     out[b,:,i] = act(bn(max_k W [x_i ; x_j(i,k) - x_i])),   W = [Wa | Wb] (H x 2C),  act = LeakyReLU(slope)
+//     (slope == 0, ReLU, and a residual behind the activation through apn_ec_out_res / apn_ec_bwd_prep_act: DeepGCN)
 //
 // The convolution is linear in [x_i ; x_j - x_i], so it is hoisted to the points: u = (Wa - Wb) x, v = Wb x (one
 // contraction, csrc/pointwise.hip, rows [u | v] of pitch ld >= 2H), y[i,k] = u_i + v_j(i,k).  BatchNorm + LeakyReLU
-// is monotone per channel with the sign of gamma (slope > 0), so the extremum over K commutes with them:
+// is monotone per channel with the sign of gamma (slope >= 0: non-decreasing is enough), so the extremum over K commutes with them:
 //
 //     out[b,c,i] = act(scale_c ext_k y[i,k][c] + shift_c),   ext = max (gamma_c >= 0) | min
 //
@@ -141,10 +142,13 @@ __global__ __launch_bounds__(256) void ec_pool_fwd_kernel(long long nq, int n, i
 
 __device__ __forceinline__ float ec_act_slope(float z, float slope) { return z > 0.0f ? 1.0f : slope; }
 
-// out (B,H,N) = act(scale ext + shift) from ext (B,N,H).  Block = 64 points x 64 channels through an LDS tile.
+// out (B,H,N) = act(scale ext + shift) [+ res] from ext (B,N,H).  Block = 64 points x 64 channels through an LDS
+// tile.  RES: res (B,H,N; element strides rs_*) is added after the activation (a ResDynBlock's `body(x) + x`).
+template <bool RES>
 __global__ __launch_bounds__(256) void ec_out_kernel(int n, int H, const float *__restrict__ ext,
                                                      const float *__restrict__ pack, float slope,
-                                                     float *__restrict__ out) {
+                                                     const float *__restrict__ res, long long rs_b, long long rs_c,
+                                                     long long rs_n, float *__restrict__ out) {
     __shared__ float tile[64][65];
     const int b = blockIdx.z, c0 = blockIdx.y * 64, p0 = blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -159,7 +163,15 @@ __global__ __launch_bounds__(256) void ec_out_kernel(int n, int H, const float *
     __syncthreads();
     const int p = p0 + tx;
     if (p < n)
-        for (int cc = ty; cc < 64; cc += 4) out[((size_t)b * H + c0 + cc) * n + p] = tile[tx][cc];
+        for (int cc = ty; cc < 64; cc += 4) {
+            float o = tile[tx][cc];
+            if constexpr (RES) {
+                float r = res[b * rs_b + (long long)(c0 + cc) * rs_c + p * rs_n];
+                asm volatile("" : "+v"(r));        // (one scalar add per element: the unrolled loop's adds are not paired)
+                o += r;
+            }
+            out[((size_t)b * H + c0 + cc) * n + p] = o;
+        }
 }
 
 // g (B,H,N; strides gs_*) -> gsel (B,N,H) = g act'(z) scale, z = scale ext + shift, and
@@ -397,8 +409,25 @@ extern "C" int apn_ec_out(int b, int n, int c, const float *ext, const float *pa
     if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope > 0.0f)) return APN_EINVAL;
     if (b == 0 || n == 0) return APN_OK;
     if (!ext || !pack || !out) return APN_EINVAL;
-    hipLaunchKernelGGL(ec_out_kernel, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, ext, pack,
-                       slope, out);
+    hipLaunchKernelGGL(ec_out_kernel<false>, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, ext,
+                       pack, slope, nullptr, 0ll, 0ll, 0ll, out);
+    APN_LAUNCH_CHECK();
+    return APN_OK;
+}
+
+// apn_ec_out with ReLU (slope == 0) allowed and an optional residual added behind the activation
+extern "C" int apn_ec_out_res(int b, int n, int c, const float *ext, const float *pack, float slope, const float *res,
+                              long long rs_b, long long rs_c, long long rs_n, float *out, void *stream) {
+    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope >= 0.0f)) return APN_EINVAL;
+    if (b == 0 || n == 0) return APN_OK;
+    if (!ext || !pack || !out) return APN_EINVAL;
+    const dim3 grid((n + 63) / 64, c / 64, b);
+    if (res)
+        hipLaunchKernelGGL(ec_out_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, n, c, ext, pack, slope, res, rs_b,
+                           rs_c, rs_n, out);
+    else
+        hipLaunchKernelGGL(ec_out_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, n, c, ext, pack, slope, nullptr,
+                           0ll, 0ll, 0ll, out);
     APN_LAUNCH_CHECK();
     return APN_OK;
 }
@@ -409,6 +438,20 @@ extern "C" int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs
                                const float *ext, const float *pack, float slope, float *gsel, float *part_s,
                                void *stream) {
     if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope > 0.0f)) return APN_EINVAL;
+    if (b == 0 || n == 0) return APN_OK;
+    if (!g || !ext || !pack || !gsel || !part_s) return APN_EINVAL;
+    hipLaunchKernelGGL(ec_bwd_prep_kernel, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, g,
+                       gs_b, gs_c, gs_n, ext, pack, slope, gsel, part_s);
+    APN_LAUNCH_CHECK();
+    return APN_OK;
+}
+
+// apn_ec_bwd_prep with ReLU (slope == 0) allowed: act' is recomputed from ext and pack, so a residual added behind the
+// activation needs nothing here (its gradient is g itself)
+extern "C" int apn_ec_bwd_prep_act(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
+                                   const float *ext, const float *pack, float slope, float *gsel, float *part_s,
+                                   void *stream) {
+    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope >= 0.0f)) return APN_EINVAL;
     if (b == 0 || n == 0) return APN_OK;
     if (!g || !ext || !pack || !gsel || !part_s) return APN_EINVAL;
     hipLaunchKernelGGL(ec_bwd_prep_kernel, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, g,

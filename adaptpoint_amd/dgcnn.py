@@ -11,7 +11,8 @@ a reference `state_dict` loads unchanged.  What differs is how a block runs:
     runs on csrc/edge_conv.hip (`adaptpoint_amd.edge_conv`) without the (B,2C,N,K) and (B,H,N,K) tensors; whatever the
     kernels do not cover takes the composed path with a `set_abstraction._note_fallback` entry.
 
-Only what DGCNN itself uses is built: conv='edge', dilation 1, no stochastic graphs.
+Only what DGCNN itself uses is built here: conv='edge', dilation 1, no stochastic graphs.  Dilated and stochastic graphs,
+ReLU and residual blocks are `adaptpoint_amd.deepgcn`'s.
 """
 import torch
 import torch.nn as nn

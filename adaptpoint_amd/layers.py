@@ -134,6 +134,47 @@ def knn_query(support, query, k, return_dist=False):
     return (idx, d2) if return_dist else idx
 
 
+KNN_WIDE_MAX = 256
+
+
+def knn_dilated_covers(support, query, k, dilation):
+    """Whether `knn_dilated` takes these tensors: CUDA float32 (B,N,C) / (B,M,C), k * dilation <= KNN_WIDE_MAX
+    neighbours searched, k of them kept."""
+    if not (support.is_cuda and query.is_cuda and support.dtype == torch.float32 and query.dtype == torch.float32
+            and support.dim() == 3 and query.dim() == 3 and support.shape[0] == query.shape[0]
+            and support.shape[2] == query.shape[2]):
+        return False
+    B, N, C = support.shape
+    return (1 <= k <= KNN_MAX_K and dilation >= 1 and k * dilation <= min(KNN_WIDE_MAX, N) and 1 <= C <= KNN_MAX_C
+            and B <= 65535 and B * max(N, query.shape[1]) < 2 ** 24)
+
+
+@torch.no_grad()
+def knn_dilated(support, query, k, dilation=1, slots=None, return_dist=False):
+    """k of the k * dilation nearest `support` (B,N,C) rows of every `query` (B,M,C) row (csrc/knn_wide.hip): with L the
+    k * dilation smallest keys (distance, support index) in `knn_query`'s order and arithmetic, entry j is
+    L[j * dilation], or L[slots[j]] for a device int32 table `slots` of k ranks (entries outside the list are clamped
+    into it).  -> idx (B,M,k) int32 [, dist2 (B,M,k)].  One launch; no (B,M,N) tensor exists."""
+    from .fused import _call, _ptr
+    if not (support.is_cuda and query.is_cuda):
+        raise RuntimeError("adaptpoint_amd.layers needs CUDA/HIP tensors: the product path has no CPU fallback")
+    if support.dtype != torch.float32 or query.dtype != torch.float32:
+        raise RuntimeError("knn_dilated takes float32 tensors")
+    _need_contiguous(support=support, query=query)
+    B, N, C = support.shape
+    M = query.shape[1]
+    if query.shape[0] != B or query.shape[2] != C:
+        raise RuntimeError(f"knn_dilated: query {tuple(query.shape)} does not match support {tuple(support.shape)}")
+    if slots is not None and not (slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous()
+                                  and slots.numel() == k):
+        raise RuntimeError(f"knn_dilated: slots must be a contiguous device int32 tensor of k = {k} entries")
+    idx = _alloc(support, B, M, k, dtype=torch.int32)
+    d2 = _alloc(support, B, M, k) if return_dist else None
+    _call("apn_knn_dilated", support.device, B, N, M, C, k * dilation, k, dilation, _ptr(slots), support.data_ptr(),
+          query.data_ptr(), idx.data_ptr(), _ptr(d2))
+    return (idx, d2) if return_dist else idx
+
+
 # ---------------------------------------------------------------- copy operators (gradient = scatter-add)
 class _TakeRows(Function):
     """out[b, c, ...] = features[b, c, idx[b, ...]] for idx (B,M) ("gather", subsample.py:108-141)

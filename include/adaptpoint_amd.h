@@ -810,6 +810,17 @@ APN_API int apn_la_pool_bwd(int b, int n, int c, int nsample, float radius, cons
 APN_API int apn_knn_query(int b, int n, int m, int c, int k, const float *support, const float *query, int *idx,
                           float *dist2, void *stream);
 
+/* apn_knn_query to rank 256 with only the wanted ranks written (csrc/knn_wide.hip): the graph of a DeepGCN block.  With L
+ * the query's kd smallest keys (d2, support index) in ascending order -- the key and the distance arithmetic are
+ * apn_knn_query's --, idx[b,q,j] = L[slots[j]].index for a device table slots int32[k] (an entry outside [0, kd) is
+ * clamped into it: nothing is read out of bounds whatever the table holds), or L[j * dilation].index with slots NULL;
+ * dist2 (b,m,k) or NULL carries the matching distances.  1 <= kd <= 256, kd <= n, 1 <= k <= 64, k <= kd, with slots NULL
+ * dilation >= 1 and (k - 1) dilation < kd, 1 <= c <= 128, b <= 65535, b * max(n, m) < 2^24, non-null pointers:
+ * APN_EINVAL otherwise, before any HIP call; b == 0 or m == 0 is a no-op.  One launch: no synchronisation, memset,
+ * allocation, global scratch or atomics; the result is a function of the inputs alone. */
+APN_API int apn_knn_dilated(int b, int n, int m, int c, int kd, int k, int dilation, const int *slots,
+                            const float *support, const float *query, int *idx, float *dist2, void *stream);
+
 /* DGCNN's EdgeConv block, out = act(bn(max_k W [x_i ; x_j - x_i])) with W = [Wa | Wb] and act = LeakyReLU(slope), the
  * convolution hoisted to the points (csrc/edge_conv.hip): uv (b,n) rows [u (c) | v (c)] of pitch ld >= 2c (ld % 4 == 0),
  * u = (Wa - Wb) x, v = Wb x, y[i,k] = u_i + v_idx[i,k].  c in {64, 128, 256, 512}, idx (b,n,k) with 1 <= k <= 64 (indices
@@ -834,6 +845,14 @@ APN_API int apn_ec_out(int b, int n, int c, const float *ext, const float *pack,
 APN_API int apn_ec_bwd_prep_rows(int b, int n);
 APN_API int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
                             const float *ext, const float *pack, float slope, float *gsel, float *part_s, void *stream);
+/* The two entries above with slope >= 0 (0 is ReLU; negative and NaN: APN_EINVAL), for DeepGCN's blocks:
+ *   out_res: out = act(scale ext + shift) + res, res (b,c,n) with element strides rs_*, or NULL for no residual.
+ *   bwd_prep_act: apn_ec_bwd_prep; act' is recomputed from ext and pack, so the residual (gradient: g) needs nothing. */
+APN_API int apn_ec_out_res(int b, int n, int c, const float *ext, const float *pack, float slope, const float *res,
+                           long long rs_b, long long rs_c, long long rs_n, float *out, void *stream);
+APN_API int apn_ec_bwd_prep_act(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
+                                const float *ext, const float *pack, float slope, float *gsel, float *part_s,
+                                void *stream);
 APN_API int apn_ec_csr(int b, int n, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream);
 APN_API int apn_ec_pool_bwd(int b, int n, int c, int k, const float *gsel, const void *sel, const int *pcnt_poff,
                             const int *plist, const float *uv, int ld, const float *ysum, const float *de, float *duv,
