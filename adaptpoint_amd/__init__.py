@@ -7,6 +7,7 @@
     fused.py, fused_wide.py            the fused grouped MLP (32->32->64 / every width)
     pointset.py, attention.py, imitator.py, augmentor.py, discriminator.py, gan.py
                                        the AdaptPoint generator / discriminator / training steps
+    chamfer_dist.py                    Chamfer distance (the reference's `chamfer` module and its loss classes)
     dp.py      data-parallel plumbing (flat gradient all-reduce, all-reduce SyncBatchNorm)
 
 `pointnet2_batch_cuda.py` at the repository root is the drop-in module the

@@ -169,6 +169,9 @@ SIGNATURES = {
     "apn_ec_bwd_prep_act": [_c_int] * 3 + [_c_void_p] + [_c_longlong] * 3 + [_c_void_p] * 2 + [_c_float] + [_c_void_p] * 3,
     "apn_ec_csr": [_c_int] * 3 + [_c_void_p] * 5,
     "apn_ec_pool_bwd": [_c_int] * 4 + [_c_void_p] * 5 + [_c_int] + [_c_void_p] * 4,
+    "apn_chamfer_max_points": [],
+    "apn_chamfer_forward": [_c_int] * 3 + [_c_void_p] * 7,
+    "apn_chamfer_backward": [_c_int] * 3 + [_c_void_p] * 9,
 }
 
 _lib = None

@@ -858,6 +858,28 @@ APN_API int apn_ec_pool_bwd(int b, int n, int c, int k, const float *gsel, const
                             const int *plist, const float *uv, int ld, const float *ysum, const float *de, float *duv,
                             void *stream);
 
+/* Chamfer distance between the clouds xyz1 (b,n,3) and xyz2 (b,m,3), the reference's `chamfer` module
+ * (csrc/chamfer.hip); dist1 / idx1 / grad_dist1 are (b,n), dist2 / idx2 / grad_dist2 (b,m), everything contiguous.
+ *   forward: dist1[b,i] = min_j d(xyz1[b,i], xyz2[b,j]) and idx1[b,i] = the SMALLEST j that attains it (strict `<` over
+ *     ascending j, as the reference's kernel decides), with d = fma(tz, tz, fma(ty, ty, tx * tx)), t = xyz2_j - xyz1_i, in
+ *     fp32: apn_knn_query's form at c = 3 (the library is built with -ffp-contract=off: this is the only fma).  dist2 /
+ *     idx2: the same with the clouds' roles swapped.  Inputs are assumed finite.
+ *   backward: for every i, per component, in fp32 with separately rounded operations in exactly this order:
+ *         acc = (grad_dist1[i] * 2) * (xyz1[i] - xyz2[idx1[i]])
+ *         for j ascending with idx2[j] == i:   acc = acc - (grad_dist2[j] * 2) * (xyz2[j] - xyz1[i])
+ *         grad_xyz1[i] = acc
+ *     and grad_xyz2 symmetrically.  Every output element is written (nothing has to arrive zeroed); there is no float
+ *     atomic, the result is a pure function of the inputs; indices outside the other cloud are clamped into it.
+ * 1 <= n, m <= apn_chamfer_max_points() = 65536, b * max(n, m) < 2^24 (no limit on b beyond that: the grids are flat),
+ * non-null pointers: APN_EINVAL otherwise, before any HIP call; b == 0 is a no-op.  One launch per entry for both
+ * directions: no synchronisation, allocation, memset or global scratch. */
+APN_API int apn_chamfer_max_points(void);
+APN_API int apn_chamfer_forward(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist1, float *dist2,
+                                int *idx1, int *idx2, void *stream);
+APN_API int apn_chamfer_backward(int b, int n, int m, const float *xyz1, const float *xyz2, const int *idx1,
+                                 const int *idx2, const float *grad_dist1, const float *grad_dist2, float *grad_xyz1,
+                                 float *grad_xyz2, void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
