@@ -404,21 +404,10 @@ extern "C" int apn_ec_pool_fwd(int b, int n, int c, int k, const float *uv, int 
     return APN_OK;
 }
 
-extern "C" int apn_ec_out(int b, int n, int c, const float *ext, const float *pack, float slope, float *out,
-                          void *stream) {
-    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope > 0.0f)) return APN_EINVAL;
-    if (b == 0 || n == 0) return APN_OK;
-    if (!ext || !pack || !out) return APN_EINVAL;
-    hipLaunchKernelGGL(ec_out_kernel<false>, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, ext,
-                       pack, slope, nullptr, 0ll, 0ll, 0ll, out);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
-}
-
-// apn_ec_out with ReLU (slope == 0) allowed and an optional residual added behind the activation
-extern "C" int apn_ec_out_res(int b, int n, int c, const float *ext, const float *pack, float slope, const float *res,
-                              long long rs_b, long long rs_c, long long rs_n, float *out, void *stream) {
-    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope >= 0.0f)) return APN_EINVAL;
+// The output stage behind its entries' slope guards: sizes, the empty-work return, pointers, the launch
+static int ec_out_launch(int b, int n, int c, const float *ext, const float *pack, float slope, const float *res,
+                         long long rs_b, long long rs_c, long long rs_n, float *out, void *stream) {
+    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535) return APN_EINVAL;
     if (b == 0 || n == 0) return APN_OK;
     if (!ext || !pack || !out) return APN_EINVAL;
     const dim3 grid((n + 63) / 64, c / 64, b);
@@ -432,12 +421,26 @@ extern "C" int apn_ec_out_res(int b, int n, int c, const float *ext, const float
     return APN_OK;
 }
 
+extern "C" int apn_ec_out(int b, int n, int c, const float *ext, const float *pack, float slope, float *out,
+                          void *stream) {
+    if (!(slope > 0.0f)) return APN_EINVAL;
+    return ec_out_launch(b, n, c, ext, pack, slope, nullptr, 0ll, 0ll, 0ll, out, stream);
+}
+
+// apn_ec_out with ReLU (slope == 0) allowed and an optional residual added behind the activation
+extern "C" int apn_ec_out_res(int b, int n, int c, const float *ext, const float *pack, float slope, const float *res,
+                              long long rs_b, long long rs_c, long long rs_n, float *out, void *stream) {
+    if (!(slope >= 0.0f)) return APN_EINVAL;
+    return ec_out_launch(b, n, c, ext, pack, slope, res, rs_b, rs_c, rs_n, out, stream);
+}
+
 extern "C" int apn_ec_bwd_prep_rows(int b, int n) { return (b <= 0 || n <= 0) ? 0 : b * ((n + 63) / 64); }
 
-extern "C" int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
-                               const float *ext, const float *pack, float slope, float *gsel, float *part_s,
-                               void *stream) {
-    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope > 0.0f)) return APN_EINVAL;
+// The backward pass's first stage behind its entries' slope guards, as ec_out_launch
+static int ec_bwd_prep_launch(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
+                              const float *ext, const float *pack, float slope, float *gsel, float *part_s,
+                              void *stream) {
+    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535) return APN_EINVAL;
     if (b == 0 || n == 0) return APN_OK;
     if (!g || !ext || !pack || !gsel || !part_s) return APN_EINVAL;
     hipLaunchKernelGGL(ec_bwd_prep_kernel, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, g,
@@ -446,18 +449,20 @@ extern "C" int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs
     return APN_OK;
 }
 
+extern "C" int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
+                               const float *ext, const float *pack, float slope, float *gsel, float *part_s,
+                               void *stream) {
+    if (!(slope > 0.0f)) return APN_EINVAL;
+    return ec_bwd_prep_launch(b, n, c, g, gs_b, gs_c, gs_n, ext, pack, slope, gsel, part_s, stream);
+}
+
 // apn_ec_bwd_prep with ReLU (slope == 0) allowed: act' is recomputed from ext and pack, so a residual added behind the
 // activation needs nothing here (its gradient is g itself)
 extern "C" int apn_ec_bwd_prep_act(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
                                    const float *ext, const float *pack, float slope, float *gsel, float *part_s,
                                    void *stream) {
-    if (b < 0 || n < 0 || b > 65535 || c <= 0 || (c % 64) || c / 64 > 65535 || !(slope >= 0.0f)) return APN_EINVAL;
-    if (b == 0 || n == 0) return APN_OK;
-    if (!g || !ext || !pack || !gsel || !part_s) return APN_EINVAL;
-    hipLaunchKernelGGL(ec_bwd_prep_kernel, dim3((n + 63) / 64, c / 64, b), dim3(256), 0, (hipStream_t)stream, n, c, g,
-                       gs_b, gs_c, gs_n, ext, pack, slope, gsel, part_s);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    if (!(slope >= 0.0f)) return APN_EINVAL;
+    return ec_bwd_prep_launch(b, n, c, g, gs_b, gs_c, gs_n, ext, pack, slope, gsel, part_s, stream);
 }
 
 extern "C" int apn_ec_csr(int b, int n, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream) {

@@ -1,6 +1,8 @@
-// knn.hip -- exact brute-force k nearest neighbours of C-dimensional rows (apn_knn_query).
+// knn.hip -- exact brute-force k nearest neighbours of C-dimensional rows: apn_knn_query (the k nearest, k <= 64) and
+// apn_knn_dilated (to rank 256 with only the wanted ranks written: the graph of a DeepGCN block, the k*d nearest rows of
+// every row thinned to k of them -- openpoints/models/layers/graph_conv.py, DilatedKNN).  One kernel serves both.
 //
-// Contract (include/adaptpoint_amd.h): for every query the k supports with the smallest key (d2, support index), in
+// Contract (include/adaptpoint_amd.h): for every query the kd supports with the smallest key (d2, support index), in
 // ascending key order, where
 //
 //      d2(q, s) = sum_c (q_c - s_c)^2       in fp32, by direct differences, accumulated over c = 0, 1, ..., C-1 as
@@ -17,11 +19,16 @@
 // tile's queries lie in LDS as [channel][query]: a wave fetches its KNN_QPW query values of a channel with one
 // broadcast 16-byte read, so one support word serves KNN_QPW subtract + fma pairs.
 //
-// The running top-k of a query lives in the wave's lanes: lane j holds the j-th smallest (d2, index) seen so far
-// (+inf beyond what has been seen).  Supports are visited in ascending index order, so a candidate that ties an entry
-// of the list has the larger index and goes BEHIND it: insertion shifts only the entries strictly greater than the
-// candidate, and a candidate enters only when it is strictly below the k-th entry.  A ballot against that k-th
-// distance gates the serial insertion; after the first few chunks almost no lane passes it.
+// The running list of a query lives in the wave's lanes, R = ceil(kd / 64) registers per lane: rank r lives in register
+// r / 64, lane r % 64 (+inf beyond what has been seen); apn_knn_query is R = 1, lane j holding the j-th smallest.
+// Supports are visited in ascending index order, so a candidate that ties an entry of the list has the larger index and
+// goes BEHIND it: insertion moves only the entries strictly greater than the candidate one rank up -- a DPP shift
+// inside a register, lane 63 of register j - 1 carried into lane 0 of register j -- and walks the registers from the top
+// down, stopping at the first one whose last entry is not greater than the candidate (nothing below it moves).  A
+// candidate enters only when it is strictly below the kd-th entry (rank kd - 1, always in register R - 1): a ballot
+// against that distance gates the serial insertion; after the first few chunks almost no lane passes it.  At the end
+// lane j < k fetches rank slots[j] (clamped into [0, kd)) or j * dilation with one cross-lane read of the distance and
+// one of the index per register: one launch, no global scratch, no atomics, a function of the inputs alone.
 #include "apn_common.h"
 
 namespace apn {
@@ -32,9 +39,10 @@ constexpr int KNN_TILE = KNN_WAVES * KNN_QPW;           // queries per workgroup
 constexpr int KNN_THREADS = KNN_WAVES * APN_WAVE;
 constexpr int KNN_CHUNK_WORDS = 8192;                   // support words staged per chunk (32 KiB)
 constexpr int KNN_CHUNK_MAX = 1024;
+constexpr int KNN_KD_MAX = 256;                         // ranks searched: at most 4 registers per lane
 
 // supports per chunk: a multiple of the wave width, chunk * c <= KNN_CHUNK_WORDS (c <= 128 -> at least 64)
-__host__ __device__ inline int knn_chunk(int n, int c) {
+static inline int knn_chunk(int n, int c) {
     int ch = (KNN_CHUNK_WORDS / c) & ~(APN_WAVE - 1);
     if (ch > KNN_CHUNK_MAX) ch = KNN_CHUNK_MAX;
     const int need = (n + APN_WAVE - 1) & ~(APN_WAVE - 1);
@@ -47,30 +55,42 @@ __device__ __forceinline__ int wave_shr1(int v) {
 }
 
 // one wave's 64 candidates (d, s: one per lane, ascending index with the lane) into the sorted list (ld, li)
-__device__ __forceinline__ void knn_insert(float &ld, int &li, float d, int s, int k, int lane) {
-    float thr = readlane_f(ld, k - 1);
+template <int R>
+__device__ __forceinline__ void knn_insert(float (&ld)[R], int (&li)[R], float d, int s, int tl, int lane) {
+    float thr = readlane_f(ld[R - 1], tl);               // the kd-th distance: rank kd - 1 = (R - 1) * 64 + tl
     unsigned long long mask = __ballot(d < thr);
     while (mask) {
         const int l = __builtin_ctzll(mask);
         mask &= mask - 1;
         const float cd = readlane_f(d, l);
-        if (!(cd < thr)) continue;                       // the k-th distance has dropped below this candidate
+        if (!(cd < thr)) continue;                       // the kd-th distance has dropped below this candidate
         const int ci = __builtin_amdgcn_readlane(s, l);
-        const float pd = __int_as_float(wave_shr1(__float_as_int(ld)));
-        const int pi = wave_shr1(li);
-        if (ld > cd) {                                   // strictly greater entries move one lane up
-            const bool prev = lane > 0 && pd > cd;
-            ld = prev ? pd : cd;
-            li = prev ? pi : ci;
+#pragma unroll
+        for (int j = R - 1; j >= 0; --j) {               // top down: register j - 1 is still the old one when j reads it
+            // (wave-uniform) nothing at or below this register moves; the top one always does: its last entry >= thr > cd
+            if (j < R - 1 && !(readlane_f(ld[j], 63) > cd)) break;
+            float pd = __int_as_float(wave_shr1(__float_as_int(ld[j])));
+            int pi = wave_shr1(li[j]);
+            if (j > 0) {
+                const float cdn = readlane_f(ld[j - 1], 63);
+                const int cin = __builtin_amdgcn_readlane(li[j - 1], 63);
+                if (lane == 0) { pd = cdn; pi = cin; }
+            }
+            if (ld[j] > cd) {                            // strictly greater entries move one rank up
+                const bool prev = (j > 0 || lane > 0) && pd > cd;
+                ld[j] = prev ? pd : cd;
+                li[j] = prev ? pi : ci;
+            }
         }
-        thr = readlane_f(ld, k - 1);
+        thr = readlane_f(ld[R - 1], tl);
     }
 }
 
-__global__ __launch_bounds__(KNN_THREADS) void knn_kernel(int n, int m, int c, int k, int chunk,
+template <int R>
+__global__ __launch_bounds__(KNN_THREADS) void knn_kernel(int n, int m, int c, int kd, int k, int dilation,
+                                                           int chunk, const int *__restrict__ slots,
                                                            const float *support, const float *query,   // may alias
-                                                           int *__restrict__ idx,
-                                                           float *__restrict__ dist2) {
+                                                           int *__restrict__ idx, float *__restrict__ dist2) {
     extern __shared__ __align__(16) float lds[];
     float *qs = lds;                                     // [c][KNN_TILE]
     float *ss = lds + c * KNN_TILE;                      // [c][chunk + 1]
@@ -80,6 +100,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(int n, int m, int c, i
     const int wave = tid / APN_WAVE;
     const int bi = blockIdx.y;
     const int q0 = blockIdx.x * KNN_TILE;
+    const int tl = (kd - 1) & (APN_WAVE - 1);
     const float *sup = support + (size_t)bi * n * c;
     const float *qry = query + (size_t)bi * m * c;
 
@@ -91,12 +112,15 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(int n, int m, int c, i
         qs[ci * KNN_TILE + qi] = qry[(size_t)q * c + ci];
     }
 
-    float ld[KNN_QPW];
-    int li[KNN_QPW];
+    float ld[KNN_QPW][R];
+    int li[KNN_QPW][R];
 #pragma unroll
     for (int t = 0; t < KNN_QPW; ++t) {
-        ld[t] = __builtin_inff();
-        li[t] = 0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            ld[t][j] = __builtin_inff();
+            li[t][j] = 0;
+        }
     }
 
     for (int s0 = 0; s0 < n; s0 += chunk) {
@@ -136,37 +160,72 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(int n, int m, int c, i
             const int s = s0 + sl;
 #pragma unroll
             for (int t = 0; t < KNN_QPW; ++t)
-                knn_insert(ld[t], li[t], live ? acc[t] : __builtin_inff(), s, k, lane);
+                knn_insert<R>(ld[t], li[t], live ? acc[t] : __builtin_inff(), s, tl, lane);
         }
     }
 
-    if (lane < k) {
+    // lane j < k takes rank r: the table's entry clamped into [0, kd), or j * dilation
+    int r = 0;
+    if (lane < k) r = slots ? slots[lane] : lane * dilation;
+    r = r < 0 ? 0 : (r >= kd ? kd - 1 : r);
+    const int rl = r & (APN_WAVE - 1), rj = r / APN_WAVE;
 #pragma unroll
-        for (int t = 0; t < KNN_QPW; ++t) {
-            const int q = q0 + wave * KNN_QPW + t;
-            if (q < m) {
-                const size_t o = ((size_t)bi * m + q) * k + lane;
-                idx[o] = li[t];
-                if (dist2) dist2[o] = ld[t];
-            }
+    for (int t = 0; t < KNN_QPW; ++t) {
+        float od = 0.0f;
+        int oi = 0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {                    // (every lane takes part in the cross-lane reads)
+            const float vd = __shfl(ld[t][j], rl, APN_WAVE);
+            const int vi = __shfl(li[t][j], rl, APN_WAVE);
+            if (rj == j) { od = vd; oi = vi; }
+        }
+        const int q = q0 + wave * KNN_QPW + t;
+        if (lane < k && q < m) {
+            const size_t o = ((size_t)bi * m + q) * k + lane;
+            idx[o] = oi;
+            if (dist2) dist2[o] = od;
         }
     }
 }
 
 }  // namespace apn
 
-extern "C" int apn_knn_query(int b, int n, int m, int c, int k, const float *support, const float *query, int *idx,
-                             float *dist2, void *stream) {
-    using namespace apn;
-    if (b < 0 || n < 1 || m < 0 || c < 1 || c > 128 || k < 1 || k > 64 || k > n || b > 65535) return APN_EINVAL;
+using namespace apn;
+
+// what both entries ask of the sizes and the pointers, the empty-work return between them, and the launch
+static int knn_launch(int b, int n, int m, int c, int kd, int k, int dilation, const int *slots, const float *support,
+                      const float *query, int *idx, float *dist2, void *stream) {
+    if (b < 0 || n < 1 || m < 0 || c < 1 || c > 128 || b > 65535) return APN_EINVAL;
     if ((long long)b * (n > m ? n : m) >= (1ll << 24)) return APN_EINVAL;
     if (b == 0 || m == 0) return APN_OK;
     if (!support || !query || !idx) return APN_EINVAL;
     const int chunk = knn_chunk(n, c);
     const size_t lds = sizeof(float) * ((size_t)c * KNN_TILE + (size_t)c * (chunk + 1));      // <= 8 + 32.5 KiB
-    dim3 grid((m + KNN_TILE - 1) / KNN_TILE, b);
-    hipLaunchKernelGGL(knn_kernel, grid, dim3(KNN_THREADS), lds, (hipStream_t)stream, n, m, c, k, chunk, support, query,
-                       idx, dist2);
+    const dim3 grid((m + KNN_TILE - 1) / KNN_TILE, b), block(KNN_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+#define APN_KNN(R)                                                                                                 \
+    hipLaunchKernelGGL(knn_kernel<R>, grid, block, lds, st, n, m, c, kd, k, dilation, chunk, slots, support, query, \
+                       idx, dist2)
+    switch ((kd + APN_WAVE - 1) / APN_WAVE) {
+        case 1: APN_KNN(1); break;
+        case 2: APN_KNN(2); break;
+        case 3: APN_KNN(3); break;
+        default: APN_KNN(4); break;
+    }
+#undef APN_KNN
     APN_LAUNCH_CHECK();
     return APN_OK;
+}
+
+extern "C" int apn_knn_query(int b, int n, int m, int c, int k, const float *support, const float *query, int *idx,
+                             float *dist2, void *stream) {
+    if (k < 1 || k > 64 || k > n) return APN_EINVAL;
+    return knn_launch(b, n, m, c, k, k, 1, nullptr, support, query, idx, dist2, stream);     // R = 1, ranks 0 .. k-1
+}
+
+extern "C" int apn_knn_dilated(int b, int n, int m, int c, int kd, int k, int dilation, const int *slots,
+                               const float *support, const float *query, int *idx, float *dist2, void *stream) {
+    if (kd < 1 || kd > KNN_KD_MAX || kd > n || k < 1 || k > 64 || k > kd) return APN_EINVAL;
+    if (!slots && (dilation < 1 || (long long)(k - 1) * dilation >= kd)) return APN_EINVAL;
+    return knn_launch(b, n, m, c, kd, k, dilation, slots, support, query, idx, dist2, stream);
 }

@@ -8,10 +8,12 @@ Attribute names are the reference's (`head.gconv.nn.{0,1}.*`, `backbone.<i>.body
 differs is how a block runs:
 
   * the dilated graph -- the reference's `cdist(x, x).topk(k d)` over a (B,N,N) tensor, then k of the k d columns --
-    comes from `layers.knn_dilated` (csrc/knn_wide.hip, k d <= 256) in one launch that writes only the k wanted ranks;
+    comes from `layers.knn_dilated` (csrc/knn.hip, k d <= 256) in one launch that writes only the k wanted ranks;
     CPU tensors keep the reference's lines, k d > 256 on the GPU takes them with a `_note_fallback` entry;
   * with fused=True an EdgeConv block runs on csrc/edge_conv.hip with ReLU (slope 0) and, in a `ResDynBlock`, the
     residual added in the output kernel (`edge_conv.edge_conv(..., residual=x)`): `body(x) + x` without another pass.
+
+`EdgeConv`, `GraphConv` and the bases of the backbone and the classifier are `adaptpoint_amd.dgcnn`'s.
 
 Random draws (stochastic=True) are the reference's, on the host from torch's CPU generator, in its order and number:
 every `DilatedKNN.forward` draws `torch.rand(1)` -- in eval mode too -- and `torch.randperm(k d)[:k]` only when training
@@ -28,10 +30,9 @@ them against.
 import torch
 import torch.nn as nn
 
-from . import dgcnn as _dg
 from . import edge_conv as _ec
+from .dgcnn import LEAKY, EdgeConv, GraphBackbone, GraphClassifier, GraphConv, _gconv      # noqa: F401 (EdgeConv: this module's too)
 from .layers import knn_dilated, knn_dilated_covers
-from .pointnext import ClsHead, SmoothCrossEntropy
 from .set_abstraction import convblock
 
 RELU = {'act': 'relu'}
@@ -100,72 +101,6 @@ class DilatedKNN(nn.Module):
         return self._dilated(idx, self.slots)
 
 
-class EdgeConv(_dg.EdgeConv):
-    """`dgcnn.EdgeConv` with ReLU or LeakyReLU and an optional residual (B,H,N,1) added behind the max:
-    forward(x, edge_index, residual=None) = max_k nn([x_i ; x_j - x_i]) [+ residual]."""
-
-    def _slope(self):
-        act = self.nn[2]
-        return 0.0 if isinstance(act, nn.ReLU) else act.negative_slope
-
-    def _uncovered(self, x, K):
-        blk = tuple(self.nn)
-        ok = (len(blk) == 3 and isinstance(blk[0], nn.Conv2d) and isinstance(blk[1], nn.BatchNorm2d)
-              and (isinstance(blk[2], nn.ReLU) or (isinstance(blk[2], nn.LeakyReLU) and blk[2].negative_slope >= 0))
-              and (blk[1].training or blk[1].track_running_stats) and blk[1].affine
-              and not (self.nn._forward_hooks or self.nn._forward_pre_hooks or blk[0]._forward_hooks or blk[1]._forward_hooks))
-        if ok:
-            ok = _ec.covers(x.shape[0], x.shape[2], K, x.shape[1], blk[0].out_channels, blk[0].bias is not None,
-                            blk[1].momentum)
-        if ok:
-            return None
-        return (f"EdgeConv C_in={x.shape[1]} -> {blk[0].out_channels}, K={K}: no fused kernel for this block")
-
-    def forward(self, x, edge_index, residual=None):
-        from .set_abstraction import _note_fallback, _ranks
-        graph = edge_index if isinstance(edge_index, _ec.EdgeIndex) else None
-        idx = graph.idx if graph is not None else edge_index
-        if self.fused and x.is_cuda and x.dtype == torch.float32:
-            reason = self._uncovered(x, idx.shape[-1])
-            if self.sync_bn and _ranks() > 1:
-                raise RuntimeError("EdgeConv(fused=True, sync_bn=True): the fused block has no BatchNorm exchange over "
-                                   "ranks and never normalises rank-locally: convert the BatchNorm modules "
-                                   "(adaptpoint_amd.dp.convert_sync_batchnorm) and build the block with fused=False")
-            if reason is None:
-                if graph is None:
-                    graph = _ec.edge_index(idx)
-                blk = tuple(self.nn)
-                xs = x.squeeze(-1)
-                res = None if residual is None else (xs if residual is x else residual.squeeze(-1))
-                return _ec.edge_conv(xs, graph, blk[0], blk[1], self._slope(), residual=res).unsqueeze(-1)
-            _note_fallback(reason)
-        x_j = _dg._group(x.squeeze(-1), idx)
-        y = self.nn(torch.cat([x.expand(-1, -1, -1, idx.shape[-1]), x_j - x], dim=1))
-        y = torch.max(y, -1, keepdim=True)[0]
-        return y if residual is None else y + residual
-
-
-def _gconv(conv):
-    if conv in ('mr', 'mrconv'):
-        raise NotImplementedError("graph convolution 'mr' cannot run in the reference either ('mr' is a KeyError in its "
-                                  "layer table and MRConv.forward calls x.unsequence, which does not exist): there is "
-                                  "nothing to pin it against")
-    if conv not in ('edge', 'edgeconv') and conv is not EdgeConv:
-        raise NotImplementedError(f"graph convolution '{conv}' is outside the hot-path build (DeepGCN uses 'edge')")
-    return EdgeConv
-
-
-class GraphConv(nn.Module):
-    """graph_conv.py:61-72: a graph convolution on a graph that is handed in."""
-
-    def __init__(self, in_channels, out_channels, conv='edge', fused=False, **kwargs):
-        super().__init__()
-        self.gconv = _gconv(conv)(in_channels, out_channels, fused=fused, **kwargs)
-
-    def forward(self, x, edge_index, residual=None):
-        return self.gconv(x, edge_index, residual)
-
-
 class DynConv(GraphConv):
     """graph_conv.py:75-89: the graph is the dilated kNN of the block's own input, rebuilt every forward.
     `forward(x, edge_index=None, residual=None)`: edge_index = neighbours computed ahead (then nothing is drawn); the
@@ -200,7 +135,7 @@ class ResDynBlock(nn.Module):
         return self.body(x, edge_index, residual=x)
 
 
-class DeepGCN(nn.Module):
+class DeepGCN(GraphBackbone):
     """deepgcn.py:13-128: a static EdgeConv on the coordinates' graph, n_blocks - 1 dynamic blocks of constant width
     (block='res': residual, dilation 1 + i with use_dilation, stochastic with use_stochastic; 'plain': neither), all
     outputs concatenated into a Conv1d-BN-LeakyReLU(0.2) fusion block; forward_cls_feat pools it to cat(max, mean).
@@ -214,7 +149,7 @@ class DeepGCN(nn.Module):
         act_args = dict(RELU) if act_args is None else act_args
         conv_args = {'order': 'conv-norm-act'} if conv_args is None else conv_args
         _gconv(conv)
-        self.n_blocks, self.k = n_blocks, k
+        self.n_blocks, self.k, self.n_graphs = n_blocks, k, n_blocks
         common = dict(fused=fused, sync_bn=sync_bn, act_args=act_args, norm_args=norm_args, **conv_args)
         self.knn = DilatedKNN(k, 1, use_stochastic, epsilon)
         self.head = GraphConv(in_channels, channels, conv, bias=False, **common)
@@ -229,12 +164,10 @@ class DeepGCN(nn.Module):
         else:       # plain GCN: no dilation, no stochastic graphs, no residual connections
             self.backbone = nn.Sequential(*[DynConv(channels, channels, conv, k, 1, False, epsilon, **common)
                                             for i in range(n_blocks - 1)])
-        self.fusion_block = convblock(int(channels * n_blocks), emb_dims, 1, norm_args=norm_args, act_args=dict(_dg.LEAKY),
+        self.fusion_block = convblock(int(channels * n_blocks), emb_dims, 1, norm_args=norm_args, act_args=dict(LEAKY),
                                       bias=False, **conv_args)
         self.model_init()
         self.out_channels = emb_dims if is_seg else emb_dims * 2
-        self.keep_graphs = False       # keep every forward's graphs in last_graphs (as the keep_graphs argument does for one call)
-        self.last_graphs = None
 
     def model_init(self):
         for m in self.modules():
@@ -256,55 +189,13 @@ class DeepGCN(nn.Module):
         for m in self.graph_modules():
             m.redraw()
 
-    def _features(self, pts, features, graphs, keep_graphs):
-        if hasattr(pts, 'keys'):
-            pts, features = pts['pos'], pts['x']
-        if features is None:
-            features = pts.transpose(1, 2).contiguous()
-        if features.dim() < 4:
-            features = features.unsqueeze(-1)
-        if graphs is not None and len(graphs) != self.n_blocks:
-            raise ValueError(f"DeepGCN: {self.n_blocks} graphs expected, {len(graphs)} given")
-        g0 = graphs[0] if graphs is not None else self.knn(pts.detach())
-        feats = [self.head(features, g0)]
-        used = [g0.idx if isinstance(g0, _ec.EdgeIndex) else g0]
-        for i, blk in enumerate(self.backbone):
-            feats.append(blk(feats[-1], None if graphs is None else graphs[i + 1]))
-            used.append(blk.last_graph)
-        self.last_graphs = used if (keep_graphs or self.keep_graphs) else None
-        return self.fusion_block(torch.cat(feats, dim=1).squeeze(-1))
-
-    def forward(self, pts, features=None, graphs=None, keep_graphs=False):
-        return self._features(pts, features, graphs, keep_graphs)
-
-    def forward_seg_feat(self, pts, features=None):
-        if hasattr(pts, 'keys'):
-            pts, features = pts['pos'], pts['x']
-        return pts, self._features(pts, features, None, False)
-
-    def forward_cls_feat(self, pts, features=None, graphs=None, keep_graphs=False):
-        fusion = self._features(pts, features, graphs, keep_graphs)
-        return torch.cat((fusion.max(dim=-1)[0], fusion.mean(dim=-1)), dim=1)
+    def _head_graph(self, pts):
+        return self.knn(pts)
 
 
-class DeepGcnClassifier(nn.Module):
-    """BaseCls (classification/cls_base.py:13-39) over DeepGCN: the encoder, `DgcnnClassifier`'s ClsHead(2 emb_dims ->
-    512 -> 256 -> num_classes) with BatchNorm1d, LeakyReLU(0.2) and dropout 0.5, SmoothCrossEntropy(0.3).  The
-    repository's clouds are (x, y, z, height): in_channels = 4."""
-
-    def __init__(self, num_classes=15, in_channels=4, fused=False, **encoder_args):
-        super().__init__()
-        self.encoder = DeepGCN(in_channels=in_channels, fused=fused, **encoder_args)
-        self.prediction = ClsHead(num_classes, self.encoder.out_channels, mlps=(512, 256),
-                                  act=lambda: nn.LeakyReLU(_dg.LEAKY['negative_slope'], inplace=True))
-        self.criterion = SmoothCrossEntropy(0.3)
+class DeepGcnClassifier(GraphClassifier):
+    """`GraphClassifier` over DeepGCN: `DgcnnClassifier`'s head and criterion."""
+    encoder_class = DeepGCN
 
     def redraw(self):
         self.encoder.redraw()
-
-    def forward(self, data, graphs=None, keep_graphs=False):
-        return self.prediction(self.encoder.forward_cls_feat(data, graphs=graphs, keep_graphs=keep_graphs))
-
-    def get_logits_loss(self, data, gt, graphs=None, keep_graphs=False):
-        logits = self.forward(data, graphs=graphs, keep_graphs=keep_graphs)
-        return logits, self.criterion(logits, gt.long())

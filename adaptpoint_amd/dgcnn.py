@@ -11,8 +11,9 @@ a reference `state_dict` loads unchanged.  What differs is how a block runs:
     runs on csrc/edge_conv.hip (`adaptpoint_amd.edge_conv`) without the (B,2C,N,K) and (B,H,N,K) tensors; whatever the
     kernels do not cover takes the composed path with a `set_abstraction._note_fallback` entry.
 
-Only what DGCNN itself uses is built here: conv='edge', dilation 1, no stochastic graphs.  Dilated and stochastic graphs,
-ReLU and residual blocks are `adaptpoint_amd.deepgcn`'s.
+DGCNN itself uses conv='edge', dilation 1, no stochastic graphs, LeakyReLU and no residual.  `EdgeConv`, `GraphConv` and
+the bases of the backbone and the classifier are shared with `adaptpoint_amd.deepgcn`, which adds the dilated and
+stochastic graphs and the residual blocks: so `EdgeConv` takes ReLU and a residual too.
 """
 import torch
 import torch.nn as nn
@@ -43,7 +44,8 @@ def _group(x, idx):
 
 
 class EdgeConv(nn.Module):
-    """graph_conv.py:38-51: max_k nn([x_i ; x_j - x_i]) for x (B,C,N,1) and edge_index (B,N,K) -> (B,H,N,1).
+    """graph_conv.py:38-51: max_k nn([x_i ; x_j - x_i]) [+ residual] for x (B,C,N,1), edge_index (B,N,K) and an optional
+    residual (B,H,N,1) added behind the max -> (B,H,N,1).  The activation is ReLU or LeakyReLU(slope >= 0).
     edge_index may be an `edge_conv.EdgeIndex` (the graph with its reverse lists, built in the index step)."""
 
     def __init__(self, in_channels, out_channels, norm_args=None, act_args=None, order='conv-norm-act', fused=False,
@@ -56,7 +58,7 @@ class EdgeConv(nn.Module):
         """None when csrc/edge_conv.hip covers this call, else the reason it does not."""
         blk = tuple(self.nn)
         ok = (len(blk) == 3 and isinstance(blk[0], nn.Conv2d) and isinstance(blk[1], nn.BatchNorm2d)
-              and isinstance(blk[2], nn.LeakyReLU) and blk[2].negative_slope > 0
+              and (isinstance(blk[2], nn.ReLU) or (isinstance(blk[2], nn.LeakyReLU) and blk[2].negative_slope >= 0))
               and (blk[1].training or blk[1].track_running_stats) and blk[1].affine
               and not (self.nn._forward_hooks or self.nn._forward_pre_hooks or blk[0]._forward_hooks or blk[1]._forward_hooks))
         if ok:
@@ -66,7 +68,7 @@ class EdgeConv(nn.Module):
             return None
         return (f"EdgeConv C_in={x.shape[1]} -> {blk[0].out_channels}, K={K}: no fused kernel for this block")
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, residual=None):
         from .set_abstraction import _note_fallback, _ranks
         graph = edge_index if isinstance(edge_index, _ec.EdgeIndex) else None
         idx = graph.idx if graph is not None else edge_index
@@ -79,17 +81,25 @@ class EdgeConv(nn.Module):
             if reason is None:
                 if graph is None:
                     graph = _ec.edge_index(idx)
-                blk = tuple(self.nn)
-                return _ec.edge_conv(x.squeeze(-1), graph, blk[0], blk[1], blk[2].negative_slope).unsqueeze(-1)
+                conv, bn, act = self.nn
+                slope = 0.0 if isinstance(act, nn.ReLU) else act.negative_slope
+                xs = x.squeeze(-1)
+                res = None if residual is None else (xs if residual is x else residual.squeeze(-1))
+                return _ec.edge_conv(xs, graph, conv, bn, slope, residual=res).unsqueeze(-1)
             _note_fallback(reason)
         x_j = _group(x.squeeze(-1), idx)
         y = self.nn(torch.cat([x.expand(-1, -1, -1, idx.shape[-1]), x_j - x], dim=1))
-        return torch.max(y, -1, keepdim=True)[0]
+        y = torch.max(y, -1, keepdim=True)[0]
+        return y if residual is None else y + residual
 
 
 def _gconv(conv):
+    if conv in ('mr', 'mrconv'):
+        raise NotImplementedError("graph convolution 'mr' cannot run in the reference either ('mr' is a KeyError in its "
+                                  "layer table and MRConv.forward calls x.unsequence, which does not exist): there is "
+                                  "nothing to pin it against")
     if conv not in ('edge', 'edgeconv') and conv is not EdgeConv:
-        raise NotImplementedError(f"graph convolution '{conv}' is outside the hot-path build (DGCNN uses 'edge')")
+        raise NotImplementedError(f"graph convolution '{conv}' is outside the hot-path build (DGCNN and DeepGCN use 'edge')")
     return EdgeConv
 
 
@@ -100,8 +110,8 @@ class GraphConv(nn.Module):
         super().__init__()
         self.gconv = _gconv(conv)(in_channels, out_channels, fused=fused, **kwargs)
 
-    def forward(self, x, edge_index):
-        return self.gconv(x, edge_index)
+    def forward(self, x, edge_index, residual=None):
+        return self.gconv(x, edge_index, residual)
 
 
 class DynConv(GraphConv):
@@ -124,37 +134,16 @@ class DynConv(GraphConv):
         return super().forward(x, edge_index)
 
 
-class DGCNN(nn.Module):
-    """dgcnn.py:13-104: a static EdgeConv on the coordinates' graph, n_blocks - 2 dynamic ones (the width doubling
-    from the second on), all outputs concatenated into a Conv1d-BN-LeakyReLU fusion block; forward_cls_feat pools it
-    to cat(max, mean)."""
+class GraphBackbone(nn.Module):
+    """What DGCNN and DeepGCN share: `head` on the graph of the coordinates, the blocks of `backbone` each on the graph
+    of its own input, all outputs concatenated into `fusion_block`.  A subclass builds those three, sets `n_graphs`
+    (one per graph convolution) and says how the head's graph is made (`_head_graph`)."""
+    n_graphs = 0
+    keep_graphs = False        # keep every forward's graphs in last_graphs (as the keep_graphs argument does for one call)
+    last_graphs = None
 
-    def __init__(self, in_channels=3, channels=64, embed_dim=1024, n_blocks=5, conv='edge', k=20, norm_args=None,
-                 act_args=None, conv_args=None, is_seg=False, fused=False, sync_bn=False, **kwargs):
-        super().__init__()
-        if kwargs.get('dilation', 1) != 1 or kwargs.get('use_dilation', False) or kwargs.get('stochastic', False) \
-                or kwargs.get('use_stochastic', False):
-            raise NotImplementedError("dilated and stochastic kNN graphs are outside the hot-path build")
-        norm_args = {'norm': 'bn'} if norm_args is None else norm_args
-        act_args = dict(LEAKY) if act_args is None else act_args
-        conv_args = {'order': 'conv-norm-act'} if conv_args is None else conv_args
-        self.n_blocks, self.k = n_blocks, k
-        self.head = GraphConv(in_channels, channels, conv, fused=fused, sync_bn=sync_bn, norm_args=norm_args, act_args=act_args, **conv_args)
-        out_channels = [channels]
-        c_in = channels
-        backbone = []
-        for _ in range(n_blocks - 2):
-            backbone.append(DynConv(c_in, channels, conv, k, fused=fused, sync_bn=sync_bn, act_args=act_args, norm_args=norm_args,
-                                    **conv_args))
-            out_channels.append(channels)
-            c_in = channels
-            channels *= 2
-        self.backbone = nn.Sequential(*backbone)
-        self.fusion_block = convblock(int(sum(out_channels)), embed_dim, 1, norm_args=norm_args, act_args=act_args,
-                                      bias=False, **conv_args)
-        self.out_channels = embed_dim if is_seg else embed_dim * 2
-        self.keep_graphs = False       # keep every forward's graphs in last_graphs (as the keep_graphs argument does for one call)
-        self.last_graphs = None
+    def _head_graph(self, pts):
+        raise NotImplementedError
 
     def _features(self, pts, features, graphs, keep_graphs):
         if hasattr(pts, 'keys'):
@@ -163,9 +152,9 @@ class DGCNN(nn.Module):
             features = pts.transpose(1, 2).contiguous()
         if features.dim() < 4:
             features = features.unsqueeze(-1)
-        if graphs is not None and len(graphs) != self.n_blocks - 1:
-            raise ValueError(f"DGCNN: {self.n_blocks - 1} graphs expected, {len(graphs)} given")
-        g0 = graphs[0] if graphs is not None else knn_graph(pts.detach(), self.k)
+        if graphs is not None and len(graphs) != self.n_graphs:
+            raise ValueError(f"{type(self).__name__}: {self.n_graphs} graphs expected, {len(graphs)} given")
+        g0 = graphs[0] if graphs is not None else self._head_graph(pts.detach())
         feats = [self.head(features, g0)]
         used = [g0.idx if isinstance(g0, _ec.EdgeIndex) else g0]
         for i, blk in enumerate(self.backbone):
@@ -187,14 +176,49 @@ class DGCNN(nn.Module):
         return torch.cat((fusion.max(dim=-1)[0], fusion.mean(dim=-1)), dim=1)
 
 
-class DgcnnClassifier(nn.Module):
-    """BaseCls (classification/cls_base.py:13-39) over DGCNN: the encoder, ClsHead(2 embed_dim -> 512 -> 256 ->
+class DGCNN(GraphBackbone):
+    """dgcnn.py:13-104: a static EdgeConv on the coordinates' graph, n_blocks - 2 dynamic ones (the width doubling
+    from the second on), all outputs concatenated into a Conv1d-BN-LeakyReLU fusion block; forward_cls_feat pools it
+    to cat(max, mean)."""
+
+    def __init__(self, in_channels=3, channels=64, embed_dim=1024, n_blocks=5, conv='edge', k=20, norm_args=None,
+                 act_args=None, conv_args=None, is_seg=False, fused=False, sync_bn=False, **kwargs):
+        super().__init__()
+        if kwargs.get('dilation', 1) != 1 or kwargs.get('use_dilation', False) or kwargs.get('stochastic', False) \
+                or kwargs.get('use_stochastic', False):
+            raise NotImplementedError("dilated and stochastic kNN graphs are outside the hot-path build")
+        norm_args = {'norm': 'bn'} if norm_args is None else norm_args
+        act_args = dict(LEAKY) if act_args is None else act_args
+        conv_args = {'order': 'conv-norm-act'} if conv_args is None else conv_args
+        self.n_blocks, self.k, self.n_graphs = n_blocks, k, n_blocks - 1
+        self.head = GraphConv(in_channels, channels, conv, fused=fused, sync_bn=sync_bn, norm_args=norm_args, act_args=act_args, **conv_args)
+        out_channels = [channels]
+        c_in = channels
+        backbone = []
+        for _ in range(n_blocks - 2):
+            backbone.append(DynConv(c_in, channels, conv, k, fused=fused, sync_bn=sync_bn, act_args=act_args, norm_args=norm_args,
+                                    **conv_args))
+            out_channels.append(channels)
+            c_in = channels
+            channels *= 2
+        self.backbone = nn.Sequential(*backbone)
+        self.fusion_block = convblock(int(sum(out_channels)), embed_dim, 1, norm_args=norm_args, act_args=act_args,
+                                      bias=False, **conv_args)
+        self.out_channels = embed_dim if is_seg else embed_dim * 2
+
+    def _head_graph(self, pts):
+        return knn_graph(pts, self.k)
+
+
+class GraphClassifier(nn.Module):
+    """BaseCls (classification/cls_base.py:13-39) over `encoder_class`: the encoder, ClsHead(2 embed_dim -> 512 -> 256 ->
     num_classes) with BatchNorm1d, LeakyReLU(0.2) and dropout 0.5, SmoothCrossEntropy(0.3).  The repository's clouds are
     (x, y, z, height): in_channels = 4."""
+    encoder_class = None
 
     def __init__(self, num_classes=15, in_channels=4, fused=False, **encoder_args):
         super().__init__()
-        self.encoder = DGCNN(in_channels=in_channels, fused=fused, **encoder_args)
+        self.encoder = self.encoder_class(in_channels=in_channels, fused=fused, **encoder_args)
         self.prediction = ClsHead(num_classes, self.encoder.out_channels, mlps=(512, 256),
                                   act=lambda: nn.LeakyReLU(LEAKY['negative_slope'], inplace=True))
         self.criterion = SmoothCrossEntropy(0.3)
@@ -205,3 +229,8 @@ class DgcnnClassifier(nn.Module):
     def get_logits_loss(self, data, gt, graphs=None, keep_graphs=False):
         logits = self.forward(data, graphs=graphs, keep_graphs=keep_graphs)
         return logits, self.criterion(logits, gt.long())
+
+
+class DgcnnClassifier(GraphClassifier):
+    """`GraphClassifier` over DGCNN."""
+    encoder_class = DGCNN

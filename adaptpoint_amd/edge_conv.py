@@ -15,14 +15,15 @@ Neither the (B,2C,N,K) nor the (B,H,N,K) tensor of the composed path exists, for
     forward   [u | v] = x^T [Wa - Wb ; Wb]^T                              the contraction kernel (apn_pw_contract)
               ext, sel, ysum, BatchNorm's sums                            apn_ec_pool_fwd (+ apn_la_stats_fold)
               pack = BatchNorm's fold (running buffers updated)           apn_sa_bn_fold
-              out = act(scale ext + shift), channels first                apn_ec_out
-    backward  gsel = g act' scale, {sum g act', sum g act' yhat}          apn_ec_bwd_prep, apn_sa_wide_consts2
+              out = act(scale ext + shift) [+ residual], channels first   apn_ec_out_res
+    backward  gsel = g act' scale, {sum g act', sum g act' yhat}          apn_ec_bwd_prep_act, apn_sa_wide_consts2
               [du | dv] per point through the reverse lists               apn_ec_pool_bwd   (no float atomics)
               dL/dx = [Wa - Wb ; Wb]^T [du | dv]^T, dL/dW from [du | dv]^T x^T    the contraction kernel
 
-DeepGCN's blocks (adaptpoint_amd.deepgcn) use ReLU and a residual: `edge_conv(..., slope=0, residual=x)` takes
-apn_ec_out_res (out = act(scale ext + shift) + residual, the block's `body(x) + x` without another pass) and
-apn_ec_bwd_prep_act; ReLU is still non-decreasing, so the max over K commutes with it as above.
+DeepGCN's blocks (adaptpoint_amd.deepgcn) use ReLU and a residual: `edge_conv(..., slope=0, residual=x)` adds it in the
+output kernel (the block's `body(x) + x` without another pass); ReLU is still non-decreasing, so the max over K
+commutes with it as above.  Every block goes through these two entries, DGCNN's (slope > 0, no residual) included; the
+C interface keeps apn_ec_out and apn_ec_bwd_prep, the same launches behind a slope > 0 guard.
 
 Gradients are bit-identical from run to run.  The data-parallel BatchNorm exchange is not built here: with sync_bn at
 world size > 1 `dgcnn.EdgeConv` raises instead of normalising rank-locally.
@@ -70,12 +71,18 @@ def edge_index(idx):
     return EdgeIndex(idx, pcnt_poff, plist)
 
 
+class _Block(NamedTuple):
+    """What `_EdgeConv` needs beside its tensors."""
+    bn: torch.nn.Module        # the BatchNorm2d (its running buffers are updated)
+    slope: float               # LeakyReLU's, 0 for ReLU
+    graph: EdgeIndex
+    res_is_x: bool             # the residual is the block's own input (C == H): `res` is None, dL/dx takes g
+
+
 class _EdgeConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, mods, res=None):
-        bn, slope, graph = mods[:3]
-        res_is_x = len(mods) > 3 and mods[3]                 # the residual is the block's own input (C == H)
-        plain = slope > 0 and res is None and not res_is_x   # DGCNN's block: apn_ec_out / apn_ec_bwd_prep
+    def forward(ctx, x, w, gamma, beta, res, blk):
+        bn, slope, graph, res_is_x = blk
         x = x.contiguous()
         dev = x.device
         B, C, N = x.shape
@@ -108,20 +115,17 @@ class _EdgeConv(torch.autograd.Function):
             _call("apn_sa_bn_fold", dev, None, 0, _fz._ptr(sums), H, count, a[0], a[1], a[5], a[6], a[2], a[3], a[4],
                   1 if training else 0, pack.data_ptr(), None, 0, None)
             out = torch.empty(B, H, N, **f32)
-            if plain:
-                _call("apn_ec_out", dev, B, N, H, ext.data_ptr(), pack.data_ptr(), float(slope), out.data_ptr())
-            else:
-                r = x if res_is_x else res
-                if r is not None and (r.shape != out.shape or r.dtype != torch.float32 or r.device != dev):
-                    raise RuntimeError(f"edge_conv: residual {tuple(r.shape)} {r.dtype} does not match the output "
-                                       f"{tuple(out.shape)} float32")
-                rs = r.stride() if r is not None else (0, 0, 0)
-                _call("apn_ec_out_res", dev, B, N, H, ext.data_ptr(), pack.data_ptr(), float(slope), _fz._ptr(r), rs[0],
-                      rs[1], rs[2], out.data_ptr())
+            r = x if res_is_x else res
+            if r is not None and (r.shape != out.shape or r.dtype != torch.float32 or r.device != dev):
+                raise RuntimeError(f"edge_conv: residual {tuple(r.shape)} {r.dtype} does not match the output "
+                                   f"{tuple(out.shape)} float32")
+            rs = r.stride() if r is not None else (0, 0, 0)
+            _call("apn_ec_out_res", dev, B, N, H, ext.data_ptr(), pack.data_ptr(), slope, _fz._ptr(r), rs[0], rs[1],
+                  rs[2], out.data_ptr())
         ctx.save_for_backward(x, UV, ext, sel, ysum, pack, Wc)
         ctx.graph = graph
-        ctx.cfg = (float(slope), training, count, gamma is not None, beta is not None, w.shape)
-        ctx.res = (plain, res_is_x, res is not None)
+        ctx.cfg = (slope, training, count, gamma is not None, beta is not None, w.shape)
+        ctx.res_is_x = res_is_x
         return out
 
     @staticmethod
@@ -129,8 +133,7 @@ class _EdgeConv(torch.autograd.Function):
         x, UV, ext, sel, ysum, pack, Wc = ctx.saved_tensors
         graph = ctx.graph
         slope, training, count, has_gamma, has_beta, wshape = ctx.cfg
-        plain, res_is_x, has_res = ctx.res
-        need_x, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:4])
+        need_x, need_w, need_res = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:4]), ctx.needs_input_grad[4]
         dev = x.device
         B, C, N = x.shape
         H = ext.shape[2]
@@ -143,8 +146,8 @@ class _EdgeConv(torch.autograd.Function):
         gsel = torch.empty(B, N, H, **f32)
         partS = torch.empty(prow, 2 * H, **f32)
         gs = g.stride()
-        _call("apn_ec_bwd_prep" if plain else "apn_ec_bwd_prep_act", dev, B, N, H, g.data_ptr(), gs[0], gs[1], gs[2],
-              ext.data_ptr(), pack.data_ptr(), slope, gsel.data_ptr(), partS.data_ptr())
+        _call("apn_ec_bwd_prep_act", dev, B, N, H, g.data_ptr(), gs[0], gs[1], gs[2], ext.data_ptr(), pack.data_ptr(),
+              slope, gsel.data_ptr(), partS.data_ptr())
         small = torch.empty(4 * H, **f32)
         de, g_gamma, g_beta = small[:2 * H], small[2 * H:3 * H], small[3 * H:]
         _call("apn_sa_wide_consts2", dev, partS.data_ptr(), prow, None, H, pack.data_ptr(), count, 1 if training else 0,
@@ -158,29 +161,26 @@ class _EdgeConv(torch.autograd.Function):
             # dL/dx[b] (C x N) = Wc^T dUV[b]^T, channels first without a transposed copy
             g_x = torch.empty(B, C, N, **f32)
             pointwise.contract(B, C, N, 2 * H, Wc, 0, C, False, dUV, N * 2 * H, 2 * H, True, g_x, d_batch=C * N, ldd=N)
-            if res_is_x:
+            if ctx.res_is_x:
                 g_x += g                                     # the residual's gradient is g itself
         if need_w:
             # dL/dWc = sum_b dUV[b]^T x[b]^T in fixed-order shares; dWa = its u rows, dWb = its v rows minus them
             g_wc = torch.empty(2 * H, C, **f32)
             pointwise.contract(B, 2 * H, C, N, dUV, N * 2 * H, 2 * H, False, x, C * N, N, True, g_wc, reduce=True)
             g_w = torch.cat([g_wc[:H], g_wc[H:] - g_wc[:H]], 1).view(wshape)
-        tail = (None,) if len(ctx.needs_input_grad) < 6 else (None, g if has_res and ctx.needs_input_grad[5] else None)
+        g_res = g if need_res else None                      # (needs_input_grad is False for res = None)
         if not need_w:
-            return (g_x, None, None, None) + tail
-        return (g_x, g_w, g_gamma if has_gamma else None, g_beta if has_beta else None) + tail
+            return g_x, None, None, None, g_res, None
+        return g_x, g_w, g_gamma if has_gamma else None, g_beta if has_beta else None, g_res, None
 
 
 def edge_conv(x, graph, conv, bn, slope, residual=None):
     """act(bn(max_k conv([x_i ; x_j - x_i]))) [+ residual] on the kernels.  x (B,C,N); graph: the `EdgeIndex` of the
     neighbours (`edge_index(idx)`); conv: the bias-free Conv2d(2C, H, 1); bn: its BatchNorm2d; slope: LeakyReLU's, 0 for
     ReLU; residual (B,H,N), any strides: added behind the activation in the output kernel (`residual is x`, a
-    ResDynBlock: its gradient joins dL/dx with one add).  slope > 0 without a residual is DGCNN's block and runs
-    exactly as it did before the residual existed."""
-    if slope > 0 and residual is None:
-        return _EdgeConv.apply(x, conv.weight, bn.weight, bn.bias, (bn, float(slope), graph))
+    ResDynBlock: its gradient joins dL/dx with one add)."""
     if not slope >= 0:
         raise ValueError(f"edge_conv: slope {slope} (the max over K commutes with a non-decreasing activation only)")
-    if residual is x:
-        return _EdgeConv.apply(x, conv.weight, bn.weight, bn.bias, (bn, float(slope), graph, True))
-    return _EdgeConv.apply(x, conv.weight, bn.weight, bn.bias, (bn, float(slope), graph, False), residual)
+    res_is_x = residual is x
+    return _EdgeConv.apply(x, conv.weight, bn.weight, bn.bias, None if res_is_x else residual,
+                           _Block(bn, float(slope), graph, res_is_x))

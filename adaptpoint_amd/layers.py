@@ -99,18 +99,36 @@ def three_nn(unknown, known):
     return d2.sqrt_(), nearest
 
 
-KNN_MAX_K, KNN_MAX_C = 64, 128
+KNN_MAX_K, KNN_MAX_C, KNN_WIDE_MAX = 64, 128, 256
 
 
-def knn_covers(support, query, k):
-    """Whether `knn_query` takes these tensors: CUDA float32 (B,N,C) / (B,M,C) within the kernel's limits."""
+def _knn_covers(support, query):
+    """What `knn_covers` and `knn_dilated_covers` ask of the tensors alone."""
     if not (support.is_cuda and query.is_cuda and support.dtype == torch.float32 and query.dtype == torch.float32
             and support.dim() == 3 and query.dim() == 3 and support.shape[0] == query.shape[0]
             and support.shape[2] == query.shape[2]):
         return False
     B, N, C = support.shape
-    return (1 <= k <= min(KNN_MAX_K, N) and 1 <= C <= KNN_MAX_C and B <= 65535
-            and B * max(N, query.shape[1]) < 2 ** 24)
+    return 1 <= C <= KNN_MAX_C and B <= 65535 and B * max(N, query.shape[1]) < 2 ** 24
+
+
+def _knn_outputs(name, support, query, k, return_dist):
+    """The argument checks of `knn_query` and `knn_dilated`, and their outputs: (B, N, M, C, idx, d2 or None)."""
+    if not (support.is_cuda and query.is_cuda):
+        raise RuntimeError("adaptpoint_amd.layers needs CUDA/HIP tensors: the product path has no CPU fallback")
+    if support.dtype != torch.float32 or query.dtype != torch.float32:
+        raise RuntimeError(f"{name} takes float32 tensors")
+    _need_contiguous(support=support, query=query)
+    B, N, C = support.shape
+    M = query.shape[1]
+    if query.shape[0] != B or query.shape[2] != C:
+        raise RuntimeError(f"{name}: query {tuple(query.shape)} does not match support {tuple(support.shape)}")
+    return B, N, M, C, _alloc(support, B, M, k, dtype=torch.int32), _alloc(support, B, M, k) if return_dist else None
+
+
+def knn_covers(support, query, k):
+    """Whether `knn_query` takes these tensors: CUDA float32 (B,N,C) / (B,M,C) within the kernel's limits."""
+    return _knn_covers(support, query) and 1 <= k <= min(KNN_MAX_K, support.shape[1])
 
 
 @torch.no_grad()
@@ -119,57 +137,30 @@ def knn_query(support, query, k, return_dist=False):
     direct differences in float32, the k smallest keys (distance, support index) in ascending order -- ties go to the
     smaller index.  -> idx (B,M,k) int32 [, dist2 (B,M,k)].  No (B,M,N) tensor exists."""
     from .fused import _call, _ptr
-    if not (support.is_cuda and query.is_cuda):
-        raise RuntimeError("adaptpoint_amd.layers needs CUDA/HIP tensors: the product path has no CPU fallback")
-    if support.dtype != torch.float32 or query.dtype != torch.float32:
-        raise RuntimeError("knn_query takes float32 tensors")
-    _need_contiguous(support=support, query=query)
-    B, N, C = support.shape
-    M = query.shape[1]
-    if query.shape[0] != B or query.shape[2] != C:
-        raise RuntimeError(f"knn_query: query {tuple(query.shape)} does not match support {tuple(support.shape)}")
-    idx = _alloc(support, B, M, k, dtype=torch.int32)
-    d2 = _alloc(support, B, M, k) if return_dist else None
+    B, N, M, C, idx, d2 = _knn_outputs("knn_query", support, query, k, return_dist)
     _call("apn_knn_query", support.device, B, N, M, C, k, support.data_ptr(), query.data_ptr(), idx.data_ptr(), _ptr(d2))
     return (idx, d2) if return_dist else idx
-
-
-KNN_WIDE_MAX = 256
 
 
 def knn_dilated_covers(support, query, k, dilation):
     """Whether `knn_dilated` takes these tensors: CUDA float32 (B,N,C) / (B,M,C), k * dilation <= KNN_WIDE_MAX
     neighbours searched, k of them kept."""
-    if not (support.is_cuda and query.is_cuda and support.dtype == torch.float32 and query.dtype == torch.float32
-            and support.dim() == 3 and query.dim() == 3 and support.shape[0] == query.shape[0]
-            and support.shape[2] == query.shape[2]):
-        return False
-    B, N, C = support.shape
-    return (1 <= k <= KNN_MAX_K and dilation >= 1 and k * dilation <= min(KNN_WIDE_MAX, N) and 1 <= C <= KNN_MAX_C
-            and B <= 65535 and B * max(N, query.shape[1]) < 2 ** 24)
+    return (_knn_covers(support, query) and 1 <= k <= KNN_MAX_K and dilation >= 1
+            and k * dilation <= min(KNN_WIDE_MAX, support.shape[1]))
 
 
 @torch.no_grad()
 def knn_dilated(support, query, k, dilation=1, slots=None, return_dist=False):
-    """k of the k * dilation nearest `support` (B,N,C) rows of every `query` (B,M,C) row (csrc/knn_wide.hip): with L the
-    k * dilation smallest keys (distance, support index) in `knn_query`'s order and arithmetic, entry j is
-    L[j * dilation], or L[slots[j]] for a device int32 table `slots` of k ranks (entries outside the list are clamped
-    into it).  -> idx (B,M,k) int32 [, dist2 (B,M,k)].  One launch; no (B,M,N) tensor exists."""
+    """k of the k * dilation nearest `support` (B,N,C) rows of every `query` (B,M,C) row (`knn_query`'s kernel,
+    csrc/knn.hip, with up to four list registers per lane): with L the k * dilation smallest keys (distance, support
+    index) in `knn_query`'s order and arithmetic, entry j is L[j * dilation], or L[slots[j]] for a device int32 table
+    `slots` of k ranks (entries outside the list are clamped into it).  -> idx (B,M,k) int32 [, dist2 (B,M,k)].  One
+    launch; no (B,M,N) tensor exists."""
     from .fused import _call, _ptr
-    if not (support.is_cuda and query.is_cuda):
-        raise RuntimeError("adaptpoint_amd.layers needs CUDA/HIP tensors: the product path has no CPU fallback")
-    if support.dtype != torch.float32 or query.dtype != torch.float32:
-        raise RuntimeError("knn_dilated takes float32 tensors")
-    _need_contiguous(support=support, query=query)
-    B, N, C = support.shape
-    M = query.shape[1]
-    if query.shape[0] != B or query.shape[2] != C:
-        raise RuntimeError(f"knn_dilated: query {tuple(query.shape)} does not match support {tuple(support.shape)}")
+    B, N, M, C, idx, d2 = _knn_outputs("knn_dilated", support, query, k, return_dist)
     if slots is not None and not (slots.is_cuda and slots.dtype == torch.int32 and slots.is_contiguous()
                                   and slots.numel() == k):
         raise RuntimeError(f"knn_dilated: slots must be a contiguous device int32 tensor of k = {k} entries")
-    idx = _alloc(support, B, M, k, dtype=torch.int32)
-    d2 = _alloc(support, B, M, k) if return_dist else None
     _call("apn_knn_dilated", support.device, B, N, M, C, k * dilation, k, dilation, _ptr(slots), support.data_ptr(),
           query.data_ptr(), idx.data_ptr(), _ptr(d2))
     return (idx, d2) if return_dist else idx

@@ -810,9 +810,9 @@ APN_API int apn_la_pool_bwd(int b, int n, int c, int nsample, float radius, cons
 APN_API int apn_knn_query(int b, int n, int m, int c, int k, const float *support, const float *query, int *idx,
                           float *dist2, void *stream);
 
-/* apn_knn_query to rank 256 with only the wanted ranks written (csrc/knn_wide.hip): the graph of a DeepGCN block.  With L
- * the query's kd smallest keys (d2, support index) in ascending order -- the key and the distance arithmetic are
- * apn_knn_query's --, idx[b,q,j] = L[slots[j]].index for a device table slots int32[k] (an entry outside [0, kd) is
+/* apn_knn_query to rank 256 with only the wanted ranks written (the same kernel of csrc/knn.hip, ceil(kd / 64) list
+ * registers per lane; apn_knn_query is kd = k, dilation 1): the graph of a DeepGCN block.  With L the query's kd
+ * smallest keys (d2, support index) in ascending order, idx[b,q,j] = L[slots[j]].index for a device table slots int32[k] (an entry outside [0, kd) is
  * clamped into it: nothing is read out of bounds whatever the table holds), or L[j * dilation].index with slots NULL;
  * dist2 (b,m,k) or NULL carries the matching distances.  1 <= kd <= 256, kd <= n, 1 <= k <= 64, k <= kd, with slots NULL
  * dilation >= 1 and (k - 1) dilation < kd, 1 <= c <= 128, b <= 65535, b * max(n, m) < 2^24, non-null pointers:
@@ -845,7 +845,8 @@ APN_API int apn_ec_out(int b, int n, int c, const float *ext, const float *pack,
 APN_API int apn_ec_bwd_prep_rows(int b, int n);
 APN_API int apn_ec_bwd_prep(int b, int n, int c, const float *g, long long gs_b, long long gs_c, long long gs_n,
                             const float *ext, const float *pack, float slope, float *gsel, float *part_s, void *stream);
-/* The two entries above with slope >= 0 (0 is ReLU; negative and NaN: APN_EINVAL), for DeepGCN's blocks:
+/* The two entries above with slope >= 0 (0 is ReLU; negative and NaN: APN_EINVAL): the same two launches, which
+ * adaptpoint_amd.edge_conv takes for every block (apn_ec_out and apn_ec_bwd_prep only add the refusal of slope == 0).
  *   out_res: out = act(scale ext + shift) + res, res (b,c,n) with element strides rs_*, or NULL for no residual.
  *   bwd_prep_act: apn_ec_bwd_prep; act' is recomputed from ext and pack, so the residual (gradient: g) needs nothing. */
 APN_API int apn_ec_out_res(int b, int n, int c, const float *ext, const float *pack, float slope, const float *res,

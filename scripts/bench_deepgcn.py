@@ -1,7 +1,7 @@
 """DeepGCN's kernels against the composed forms, per block shape of the default model at B = 32, N = 1024, C = 64, k = 16
 and dilation d in {1, 4, 8, 13}, alternating in ONE process under hipGraph replay (the method of scripts/bench_dgcnn.py):
 
-  * the dilated kNN graph of the block's input: `layers.knn_dilated` (csrc/knn_wide.hip, k d neighbours searched, k
+  * the dilated kNN graph of the block's input: `layers.knn_dilated` (csrc/knn.hip, k d neighbours searched, k
     written) against `torch.cdist(x, x).topk(k d, largest=False).indices[..., ::d]`, the reference's lines, which
     materialise (B, N, N);
   * one `ResDynBlock` 64 -> 64, forward + backward in training mode: fused (csrc/edge_conv.hip with ReLU and the

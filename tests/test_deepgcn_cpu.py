@@ -228,5 +228,5 @@ def test_argument_validation_of_the_new_entries_needs_no_gpu():
         assert entry(b=0, slope=-0.1) == EINVAL and entry(b=0, slope=NAN) == EINVAL, entry.__name__
         assert entry(slope=-0.1) == EINVAL and entry(slope=NAN) == EINVAL, entry.__name__
     assert out(b=0, res=None) == 0 and out(n=0, res=None) == 0                                  # no residual
-    # the old entries still refuse ReLU
+    # apn_ec_out / apn_ec_bwd_prep still refuse ReLU
     assert lib.apn_ec_out(0, 16, 64, P, P, 0.0, P, None) == EINVAL

@@ -1,5 +1,5 @@
 """GPU suite: the DeepGCN classifier (adaptpoint_amd/deepgcn.py) with its blocks on csrc/edge_conv.hip (ReLU, the residual
-in the output kernel) and its dilated, stochastic graphs from csrc/knn_wide.hip, against the float64 restatement
+in the output kernel) and its dilated, stochastic graphs from csrc/knn.hip, against the float64 restatement
 (tests/deepgcn_reference.py) with the composed fp32 model measured beside it -- the bar of tests/test_gpu_edge_conv.py:
 per tensor at most 4 x the composed model's relative L2 distance to float64, floor 2e-6 -- and inside the training and
 evaluation steps it has to drop into.

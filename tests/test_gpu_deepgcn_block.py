@@ -5,7 +5,7 @@ restatement (tests/deepgcn_reference.py), the composed fp32 block measured besid
 The bar (the project's own, tests/test_gpu_edge_conv.py): per tensor, the fused block's relative L2 distance to float64
 may be at most 4 x the composed fp32 block's on the same input, with a floor of 2e-6.  Inputs: of 8 seeded inputs per
 shape the one whose float64 evaluation keeps its pool winners and activation gates farthest from switching -- a
-criterion of the reference alone.  idx = the dilated kNN graph of the input (csrc/knn_wide.hip), computed once."""
+criterion of the reference alone.  idx = the dilated kNN graph of the input (csrc/knn.hip), computed once."""
 import gc
 
 import pytest

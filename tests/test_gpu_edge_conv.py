@@ -256,3 +256,33 @@ def test_uncovered_shape_takes_the_composed_path_with_a_recorded_fallback(dev):
     assert sum(SA.FUSED_FALLBACKS.values()) == before + 1
     assert any("EdgeConv" in k and "96" in k for k in SA.FUSED_FALLBACKS)
     assert R.rel(res[True]['out'], res[False]['out']) < 1e-6 and R.rel(res[True]['dx'], res[False]['dx']) < 1e-6
+
+
+def test_the_slope_guarded_c_entries_equal_the_general_ones_bit_for_bit(dev):
+    """`adaptpoint_amd.edge_conv` launches through apn_ec_out_res / apn_ec_bwd_prep_act only; apn_ec_out and
+    apn_ec_bwd_prep stay in the C interface over the same launchers, so each pair called raw on the same operands writes
+    the same bits.  N = 65: one point past the 64-point tile; H = 128: two channel tiles; g (B,H,N) is a permuted view
+    of a (B,N,H) buffer, passed by its strides."""
+    from adaptpoint_amd import _lib
+    from adaptpoint_amd.fused import _call
+    B, N, H, slope = 2, 65, 128, 0.2
+    ext = torch.from_numpy(GI.seeded_normal((B, N, H), 1360).astype(np.float32)).to(dev)
+    pack = torch.from_numpy(GI.seeded_normal((4 * H,), 1361).astype(np.float32)).to(dev)
+    g = torch.from_numpy(GI.seeded_normal((B, N, H), 1362).astype(np.float32)).to(dev).permute(0, 2, 1)
+    assert g.shape == (B, H, N) and not g.is_contiguous()
+    gs = g.stride()
+    outs = [torch.full((B, H, N), float('nan'), device=dev) for _ in range(2)]
+    _call("apn_ec_out", dev, B, N, H, ext.data_ptr(), pack.data_ptr(), slope, outs[0].data_ptr())
+    _call("apn_ec_out_res", dev, B, N, H, ext.data_ptr(), pack.data_ptr(), slope, None, 0, 0, 0, outs[1].data_ptr())
+    assert not torch.isnan(outs[0]).any() and torch.equal(outs[0], outs[1])
+    rows = _lib.load().apn_ec_bwd_prep_rows(B, N)
+    assert rows == B * 2
+    res = []
+    for name in ("apn_ec_bwd_prep", "apn_ec_bwd_prep_act"):
+        gsel = torch.full((B, N, H), float('nan'), device=dev)
+        partS = torch.full((rows, 2 * H), float('nan'), device=dev)
+        _call(name, dev, B, N, H, g.data_ptr(), gs[0], gs[1], gs[2], ext.data_ptr(), pack.data_ptr(), slope,
+              gsel.data_ptr(), partS.data_ptr())
+        res.append((gsel, partS))
+    for a, b in zip(*res):
+        assert not torch.isnan(a).any() and torch.equal(a, b)

@@ -1,4 +1,4 @@
-"""GPU suite: apn_knn_dilated (csrc/knn_wide.hip) through `layers.knn_dilated` against the numpy statement of the kNN
+"""GPU suite: apn_knn_dilated (csrc/knn.hip) through `layers.knn_dilated` against the numpy statement of the kNN
 contract (tests/knn_reference.py): with L = KR.knn(support, query, kd), the result is L[..., slots].
 
 Exact cases: integer coordinates in [-4, 4] -- every squared distance is an integer <= 64 C <= 8192, exact in fp32
