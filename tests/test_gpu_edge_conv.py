@@ -16,7 +16,8 @@ import dgcnn_reference as R
 import golden_inputs as GI
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(2, 100, 3, 64, 20), (3, 77, 4, 64, 1), (4, 256, 64, 64, 20), (2, 256, 64, 128, 20), (2, 128, 128, 256, 40)]
+SHAPES = [(2, 100, 3, 64, 20), (3, 77, 4, 64, 1), (4, 256, 64, 64, 20), (2, 256, 64, 128, 20), (2, 128, 128, 256, 40),
+          (2, 96, 64, 512, 20)]
 
 
 def _edge(dev, C, H, fused, flip=False):
