@@ -8,9 +8,10 @@
     pointset.py, attention.py, imitator.py, augmentor.py, discriminator.py, gan.py
                                        the AdaptPoint generator / discriminator / training steps
     chamfer_dist.py                    Chamfer distance (the reference's `chamfer` module and its loss classes)
+    emd.py                             earth mover's distance (the reference's `emd_cuda` module and its loss module)
     dp.py      data-parallel plumbing (flat gradient all-reduce, all-reduce SyncBatchNorm)
 
-`pointnet2_batch_cuda.py` at the repository root is the drop-in module the
-reference imports.
+`pointnet2_batch_cuda.py` and `emd_cuda.py` at the repository root are the drop-in
+modules the reference imports.
 """
 __version__ = "0.2.0"

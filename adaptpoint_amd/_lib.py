@@ -172,6 +172,13 @@ SIGNATURES = {
     "apn_chamfer_max_points": [],
     "apn_chamfer_forward": [_c_int] * 3 + [_c_void_p] * 7,
     "apn_chamfer_backward": [_c_int] * 3 + [_c_void_p] * 9,
+    "apn_emd_max_points": [],
+    "apn_emd_one_launch_max": [],
+    "apn_emd_cost_parts": [_c_int],
+    "apn_emd_ratios": [_c_int] * 3 + [_c_void_p] * 6,
+    "apn_emd_match": [_c_int] * 3 + [_c_void_p] * 6,
+    "apn_emd_cost": [_c_int] * 3 + [_c_void_p] * 8,
+    "apn_emd_cost_grad": [_c_int] * 3 + [_c_void_p] * 9,
 }
 
 _lib = None

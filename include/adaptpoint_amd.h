@@ -881,6 +881,50 @@ APN_API int apn_chamfer_backward(int b, int n, int m, const float *xyz1, const f
                                  const int *idx2, const float *grad_dist1, const float *grad_dist2, float *grad_xyz1,
                                  float *grad_xyz2, void *stream);
 
+/* Earth mover's distance (approximate, by annealed soft matching) between the clouds xyz1 (b,n,3) and xyz2 (b,m,3), the
+ * reference's `emd_cuda` module (csrc/emd.hip); everything fp32 and contiguous.  The reference's `match` (b,m,n) is a sum
+ * over ten levels q = 0..9 (its j = 7 .. -2) of rank-structured weights, so two small tables determine it:
+ *         match[l,k] = sum over q ascending, from 0, of (e_q(d[l,k]) * ratio_l[q,k]) * ratio_r[q,l]
+ *   d[l,k] = fma(tz, tz, fma(ty, ty, tx * tx)), t = xyz2_l - xyz1_k (apn_knn_query's form at c = 3: the only fma),
+ *   level_q = -4^(7-q) for q < 9 and 0 for q = 9,    e_q(d) = exp2(level_q * (d * log2(e)f)), every operation rounded to
+ *   fp32 (a level is a power of two or 0, so its product is exact: d * log2(e) is rounded once per pair) and exp2 the
+ *   hardware's v_exp_f32 (1 ulp; results below 2^-126 are 0).  ONE device function is e_q for every kernel.
+ *   ratios: writes ratio_l (b,10,n) and ratio_r (b,10,m).  With multiL, multiR = (1, n / m) if n >= m else (m / n, 1) by
+ *     C INTEGER division ((7,3): multiR = 2), remainL_k = multiL and remainR_l = multiR at the start, per level q:
+ *         ratio_l[q,k] = remainL_k / (1e-9f + sum_l e_q * remainR_l)
+ *         sumr_l = (sum_k e_q * ratio_l[q,k]) * remainR_l
+ *         ratio_r[q,l] = min(remainR_l / (sumr_l + 1e-9f), 1) * remainR_l;       remainR_l = max(0, remainR_l - sumr_l)
+ *         remainL_k = max(0, remainL_k - sum_l (e_q * ratio_l[q,k]) * ratio_r[q,l])
+ *     The sums run in an order fixed by (n, m) alone -- max(n, m) <= apn_emd_one_launch_max(): one workgroup per cloud,
+ *     one launch, every sum in ascending index; beyond it 20 launches whose workgroups own 64 rows each, the sum of a
+ *     row being p_0 + p_1 + .. + p_(W-1) added in this order, W = 8 if max(n, m) >= 256 else 4, with p_w the ascending
+ *     sum over wave w's columns: the columns go by in chunks of 1024 (the last chunk has c of them), and of every chunk
+ *     wave w takes columns r w .. r (w + 1) - 1, r = 4 ceil(ceil(c / 4) / W) -- without float atomics: two runs give the
+ *     same bits.  `state` is scratch of b (n + m) floats (the remainders between the launches of the second form); it
+ *     and the outputs may arrive uninitialised.
+ *   match: writes every element of match (b,m,n) once, by the formula above (64-bit element offsets).
+ *   cost:  cost[b] = sum_{k,l} d[l,k] * match[l,k].  grad: with g = grad_cost[b],
+ *         grad1[k] = g * sum_l (xyz1_k - xyz2_l) * (2 * match[l,k]),  grad2[l] = g * sum_k (xyz2_l - xyz1_k) * (2 * match[l,k])
+ *     (match is a constant).  Both take EITHER `match` OR, with match == NULL, the two tables, from which every match[l,k]
+ *     is recomputed by the device function apn_emd_match runs: the two sources go through one template and give the
+ *     same bits.  Row sums are ordered as in the second form above; a cloud's cost is the ascending sum over k inside a
+ *     64-row tile, then the ascending sum over the tiles (`part`: scratch of b * apn_emd_cost_parts(n) floats).  Every
+ *     output element is written; no float atomics.
+ * 1 <= n, m <= apn_emd_max_points() = 8192, b * max(n, m) < 2^24, non-null pointers (match and the tables as stated):
+ * APN_EINVAL otherwise, before any HIP call; b == 0 is a no-op.  No entry allocates, memsets or synchronises. */
+APN_API int apn_emd_max_points(void);
+APN_API int apn_emd_one_launch_max(void);
+APN_API int apn_emd_cost_parts(int n);
+APN_API int apn_emd_ratios(int b, int n, int m, const float *xyz1, const float *xyz2, float *ratio_l, float *ratio_r,
+                           float *state, void *stream);
+APN_API int apn_emd_match(int b, int n, int m, const float *xyz1, const float *xyz2, const float *ratio_l,
+                          const float *ratio_r, float *match, void *stream);
+APN_API int apn_emd_cost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
+                         const float *ratio_l, const float *ratio_r, float *part, float *cost, void *stream);
+APN_API int apn_emd_cost_grad(int b, int n, int m, const float *grad_cost, const float *xyz1, const float *xyz2,
+                              const float *match, const float *ratio_l, const float *ratio_r, float *grad1, float *grad2,
+                              void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
