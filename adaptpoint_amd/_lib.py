@@ -179,6 +179,18 @@ SIGNATURES = {
     "apn_emd_match": [_c_int] * 3 + [_c_void_p] * 6,
     "apn_emd_cost": [_c_int] * 3 + [_c_void_p] * 8,
     "apn_emd_cost_grad": [_c_int] * 3 + [_c_void_p] * 9,
+    "apn_po_knn_query": [_c_int] * 4 + [_c_void_p] * 7,
+    "apn_po_ball_query": [_c_int] * 3 + [_c_float, _c_int] + [_c_void_p] * 6,
+    "apn_po_furthest_sampling": [_c_int] * 2 + [_c_void_p] * 6,
+    "apn_po_csr": [_c_int] * 3 + [_c_void_p] * 5,
+    "apn_po_grouping_fwd": [_c_int] * 4 + [_c_void_p] * 4,
+    "apn_po_grouping_bwd": [_c_int] * 4 + [_c_void_p] * 5,
+    "apn_po_interpolation_fwd": [_c_int] * 4 + [_c_void_p] * 5,
+    "apn_po_interpolation_bwd": [_c_int] * 4 + [_c_void_p] * 6,
+    "apn_po_subtraction_fwd": [_c_int] * 4 + [_c_void_p] * 5,
+    "apn_po_subtraction_bwd": [_c_int] * 4 + [_c_void_p] * 6,
+    "apn_po_aggregation_fwd": [_c_int] * 5 + [_c_void_p] * 6,
+    "apn_po_aggregation_bwd": [_c_int] * 5 + [_c_void_p] * 11,
 }
 
 _lib = None

@@ -220,19 +220,20 @@ __global__ __launch_bounds__(256) void ec_csr_init_kernel(long long npts, int *_
     if (e < npts) pcnt[e] = 0;
 }
 
-__device__ __forceinline__ long long ec_target(const int *__restrict__ idx, long long pos, int n, int K) {
+// mq: gathering rows per cloud (n for the EdgeConv graph; apn_po_csr: all m rows gather from one set of n)
+__device__ __forceinline__ long long ec_target(const int *__restrict__ idx, long long pos, int n, int mq, int K) {
     int nb = idx[pos];
     nb = nb < 0 ? 0 : (nb >= n ? n - 1 : nb);                  // the clamp of ec_pool_fwd
-    return ((pos / K) / n) * n + nb;
+    return ((pos / K) / mq) * n + nb;
 }
 
 // one thread per position.  fill = 0: count; fill = 1: write the position behind its point's cursor.
-__global__ __launch_bounds__(256) void ec_csr_count_fill_kernel(long long npos, int n, int K, int fill,
+__global__ __launch_bounds__(256) void ec_csr_count_fill_kernel(long long npos, int n, int mq, int K, int fill,
                                                                 const int *__restrict__ idx, int *__restrict__ pcnt,
                                                                 int *__restrict__ cursor, int *__restrict__ tmp) {
     const long long pos = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pos >= npos) return;
-    const long long gj = ec_target(idx, pos, n, K);
+    const long long gj = ec_target(idx, pos, n, mq, K);
     if (!fill) atomicAdd(pcnt + gj, 1);
     else tmp[atomicAdd(cursor + gj, 1)] = (int)pos;
 }
@@ -475,10 +476,36 @@ extern "C" int apn_ec_csr(int b, int n, int k, const int *idx, int *pcnt_poff, i
     hipStream_t st = (hipStream_t)stream;
     const unsigned pb = (unsigned)((npos + 255) / 256);
     hipLaunchKernelGGL(ec_csr_init_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, npts, pcnt);
-    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, k, 0, idx, pcnt, cursor, tmp);
+    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, n, k, 0, idx, pcnt, cursor, tmp);
     hipLaunchKernelGGL(ec_csr_scan_kernel, dim3(b), dim3(1024), 0, st, n, k, pcnt, poff, cursor);
-    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, k, 1, idx, pcnt, cursor, tmp);
+    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, n, k, 1, idx, pcnt, cursor, tmp);
     hipLaunchKernelGGL(ec_csr_sort_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, st, npts, pcnt, poff, tmp,
+                       plist);
+    APN_LAUNCH_CHECK();
+    return APN_OK;
+}
+
+// The reverse lists of an (m, k) index into n rows (the stacked-cloud operators of csrc/pointops.hip): apn_ec_csr's five
+// launches over one "cloud" of n rows gathered by m k positions.  m == 0: every list is empty.
+extern "C" int apn_po_csr(int n, int m, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream) {
+    if (n < 0 || m < 0 || n >= (1 << 24) || m >= (1 << 24) || k < 1 || (long long)m * k >= (1ll << 31)) return APN_EINVAL;
+    if (n == 0) return APN_OK;
+    if (!idx || !pcnt_poff || !plist || !scratch) return APN_EINVAL;
+    const long long npos = (long long)m * k;
+    int *pcnt = pcnt_poff, *poff = pcnt_poff + n;
+    int *cursor = scratch, *tmp = scratch + n;                           // scratch: n + m k ints
+    hipStream_t st = (hipStream_t)stream;
+    if (m == 0) {
+        hipLaunchKernelGGL(ec_csr_init_kernel, dim3((unsigned)((2ll * n + 255) / 256)), dim3(256), 0, st, 2ll * n, pcnt);
+        APN_LAUNCH_CHECK();
+        return APN_OK;
+    }
+    const unsigned pb = (unsigned)((npos + 255) / 256);
+    hipLaunchKernelGGL(ec_csr_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, pcnt);
+    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, m, k, 0, idx, pcnt, cursor, tmp);
+    hipLaunchKernelGGL(ec_csr_scan_kernel, dim3(1), dim3(1024), 0, st, n, k, pcnt, poff, cursor);
+    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, m, k, 1, idx, pcnt, cursor, tmp);
+    hipLaunchKernelGGL(ec_csr_sort_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (long long)n, pcnt, poff, tmp,
                        plist);
     APN_LAUNCH_CHECK();
     return APN_OK;

@@ -30,6 +30,7 @@
 // lane j < k fetches rank slots[j] (clamped into [0, kd)) or j * dilation with one cross-lane read of the distance and
 // one of the index per register: one launch, no global scratch, no atomics, a function of the inputs alone.
 #include "apn_common.h"
+#include "knn_list.h"
 
 namespace apn {
 
@@ -47,43 +48,6 @@ static inline int knn_chunk(int n, int c) {
     if (ch > KNN_CHUNK_MAX) ch = KNN_CHUNK_MAX;
     const int need = (n + APN_WAVE - 1) & ~(APN_WAVE - 1);
     return ch < need ? ch : need;
-}
-
-// lane j <- lane j-1 (lane 0 keeps `v`): one DPP move, no LDS traffic
-__device__ __forceinline__ int wave_shr1(int v) {
-    return __builtin_amdgcn_update_dpp(v, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-}
-
-// one wave's 64 candidates (d, s: one per lane, ascending index with the lane) into the sorted list (ld, li)
-template <int R>
-__device__ __forceinline__ void knn_insert(float (&ld)[R], int (&li)[R], float d, int s, int tl, int lane) {
-    float thr = readlane_f(ld[R - 1], tl);               // the kd-th distance: rank kd - 1 = (R - 1) * 64 + tl
-    unsigned long long mask = __ballot(d < thr);
-    while (mask) {
-        const int l = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const float cd = readlane_f(d, l);
-        if (!(cd < thr)) continue;                       // the kd-th distance has dropped below this candidate
-        const int ci = __builtin_amdgcn_readlane(s, l);
-#pragma unroll
-        for (int j = R - 1; j >= 0; --j) {               // top down: register j - 1 is still the old one when j reads it
-            // (wave-uniform) nothing at or below this register moves; the top one always does: its last entry >= thr > cd
-            if (j < R - 1 && !(readlane_f(ld[j], 63) > cd)) break;
-            float pd = __int_as_float(wave_shr1(__float_as_int(ld[j])));
-            int pi = wave_shr1(li[j]);
-            if (j > 0) {
-                const float cdn = readlane_f(ld[j - 1], 63);
-                const int cin = __builtin_amdgcn_readlane(li[j - 1], 63);
-                if (lane == 0) { pd = cdn; pi = cin; }
-            }
-            if (ld[j] > cd) {                            // strictly greater entries move one rank up
-                const bool prev = (j > 0 || lane > 0) && pd > cd;
-                ld[j] = prev ? pd : cd;
-                li[j] = prev ? pi : ci;
-            }
-        }
-        thr = readlane_f(ld[R - 1], tl);
-    }
 }
 
 template <int R>

@@ -925,6 +925,78 @@ APN_API int apn_emd_cost_grad(int b, int n, int m, const float *grad_cost, const
                               const float *match, const float *ratio_l, const float *ratio_r, float *grad1, float *grad2,
                               void *stream);
 
+/* Operators on STACKED clouds, the reference's `pointops_cuda` module (csrc/pointops.hip; the reverse lists: csrc/
+ * edge_conv.hip): points xyz (n,3), features (n,c), int32 offset (b) of cumulative END rows (ascending, offset[b-1] == n),
+ * so that every cloud has its own size; queries new_xyz (m,3) with their own new_offset (b), new_offset[b-1] == m.
+ * Everything is fp32 / int32 and contiguous; element offsets are 64-bit inside the kernels (the reference's int products
+ * overflow at n * nsample * c >= 2^31).  Query row q belongs to the first cloud i with q < new_offset[i]; a row at or past
+ * new_offset[b-1] is treated as belonging to the last cloud (the reference's search runs off the array there).  A cloud's
+ * rows [start, end) are clamped into [0, n].  Any index read from `idx` is clamped into [0, n).  Squared distances are
+ *         d2 = fma(tz, tz, fma(ty, ty, tx * tx)),  t = q - s      (apn_knn_query's form at c = 3: the only fma)
+ * No entry synchronises, allocates, issues a memset or reads offsets on the host; no float atomics: every result is a
+ * pure function of the inputs, two runs give the same bits.  Every output element is written except where stated.
+ *   knn_query: idx, dist2 (m,k): for every query the k rows OF ITS OWN CLOUD with the smallest key (d2, global row index)
+ *     in ascending key order, 1 <= k <= 100 (the reference's array bound); new_xyz may alias xyz.  A cloud with fewer
+ *     than k rows (or rows at d2 >= 1e10) leaves the remaining slots at idx = start of the cloud (clamped into [0, n)),
+ *     dist2 = 1e10: the reference's initial heap, which its sqrt turns into 1e5 -- a kept quirk.  The reference's heap
+ *     orders EQUAL distances by its sift history, this entry by index: the two agree wherever the k + 1 nearest distances
+ *     of a query are distinct.  One launch, no scratch.
+ *   ball_query: idx (m,nsample): the first nsample rows of the query's cloud in ascending index with d2 < radius * radius
+ *     (strict, the product rounded to fp32); the remaining slots repeat the first hit; a query without a hit writes zeros
+ *     (what the reference's pre-zeroed, unwritten row holds).  radius >= 0, nsample >= 1.
+ *   furthest_sampling: per cloud with output rows [start_m, end_m) of idx: idx[start_m] = start; every later pick is the
+ *     arg-max of the running minimum distance min(d2 to the last pick, tmp[k]); tmp (n) is in/out and arrives filled with
+ *     1e10, as in the reference.  Ties, exactly the reference's: with T = min(1024, 2^floor(log2 n_max)), row k belongs to
+ *     thread (k - start) mod T, a thread keeps its first maximum and the block tree the lower slot unless the upper one is
+ *     strictly greater -- the winner is the maximum with the smallest bit-reversed (over log2 T bits) thread id, then
+ *     the smallest k.  n_max is the largest cloud size (rows of a cloud beyond 24 * 1024 make the kernel stream from
+ *     memory; a cloud larger than n_max claims is sampled from its first max(n_max, 24 T) rows only).  A cloud with an
+ *     empty output range writes NOTHING: the reference writes idx[start_m] regardless, into the next cloud's slot -- a
+ *     dropped quirk.  The offsets are trusted (the entry is given neither n nor m).  n_max < 2^24; b == 0 or n_max == 0
+ *     is a no-op.
+ *   csr: the reverse lists of idx (m,k) into n rows: pcnt_poff = {pcnt (n), poff (n)}, plist (m k) with row j's list
+ *     plist[poff[j] .. poff[j] + pcnt[j]) = the positions i * k + slot whose (clamped) index is j, ASCENDING.  A pure
+ *     function of idx (integer atomics count; the lists are sorted afterwards).  scratch: n + m k ints.  m k < 2^31.
+ *     m == 0 gives n empty lists.
+ *   grouping: fwd out (m,k,c) = input[idx[i,s]] (n,c).  bwd grad_input[j] = the sum over j's list, in list order, of
+ *     grad_out[pos]: sequential fp32 adds STARTING FROM THE FIRST TERM (as every sum below; an empty list gives 0).
+ *   interpolation: fwd out[i,ch] = sum over slots ascending of input[idx[i,s],ch] * weight[i,s], each product rounded,
+ *     then added.  bwd grad_input[j,ch] = sum over j's list of grad_out[pos / k, ch] * weight[pos].
+ *   subtraction: fwd out[i,s,ch] = input1[i,ch] - input2[idx[i,s],ch], input1 (m,c), input2 (n,c).  bwd grad_input1[i,ch]
+ *     = sum over slots ascending of g[i,s,ch]; grad_input2[j,ch] = sum over j's list of -g[pos,ch].
+ *   aggregation: c % w_c == 0, w = ch % w_c; input (n,c), position (m,k,c), weight (m,k,w_c).  fwd out[i,ch] = sum over
+ *     slots ascending of (input[idx[i,s],ch] + position[i,s,ch]) * weight[i,s,w]: three separately rounded operations per
+ *     term.  bwd grad_position[i,s,ch] = g[i,ch] * weight[i,s,w]; grad_weight[i,s,w] = sum over the c / w_c channels with
+ *     ch % w_c == w, ascending ch, of g[i,ch] * (input[idx[i,s],ch] + position[i,s,ch]); grad_input[j,ch] = sum over j's
+ *     list of g[pos / k, ch] * weight[pos, w].
+ * 0 <= n, m < 2^24, b >= 1 (knn, ball), k >= 1, 1 <= c <= 65536, m k < 2^31, non-null pointers: APN_EINVAL otherwise,
+ * before any HIP call.  n == 0 or m == 0 is a no-op, except that the backward entries and csr with n > 0 and m == 0
+ * write the zeros / empty lists that no query leaves behind. */
+APN_API int apn_po_knn_query(int b, int n, int m, int k, const float *xyz, const float *new_xyz, const int *offset,
+                             const int *new_offset, int *idx, float *dist2, void *stream);
+APN_API int apn_po_ball_query(int b, int n, int m, float radius, int nsample, const float *xyz, const float *new_xyz,
+                              const int *offset, const int *new_offset, int *idx, void *stream);
+APN_API int apn_po_furthest_sampling(int b, int n_max, const float *xyz, const int *offset, const int *new_offset,
+                                     float *tmp, int *idx, void *stream);
+APN_API int apn_po_csr(int n, int m, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream);
+APN_API int apn_po_grouping_fwd(int n, int m, int k, int c, const float *input, const int *idx, float *out, void *stream);
+APN_API int apn_po_grouping_bwd(int n, int m, int k, int c, const float *grad_out, const int *pcnt_poff, const int *plist,
+                                float *grad_input, void *stream);
+APN_API int apn_po_interpolation_fwd(int n, int m, int k, int c, const float *input, const int *idx, const float *weight,
+                                     float *out, void *stream);
+APN_API int apn_po_interpolation_bwd(int n, int m, int k, int c, const float *grad_out, const float *weight,
+                                     const int *pcnt_poff, const int *plist, float *grad_input, void *stream);
+APN_API int apn_po_subtraction_fwd(int n, int m, int k, int c, const float *input1, const float *input2, const int *idx,
+                                   float *out, void *stream);
+APN_API int apn_po_subtraction_bwd(int n, int m, int k, int c, const float *grad_out, const int *pcnt_poff,
+                                   const int *plist, float *grad_input1, float *grad_input2, void *stream);
+APN_API int apn_po_aggregation_fwd(int n, int m, int k, int c, int w_c, const float *input, const float *position,
+                                   const float *weight, const int *idx, float *out, void *stream);
+APN_API int apn_po_aggregation_bwd(int n, int m, int k, int c, int w_c, const float *input, const float *position,
+                                   const float *weight, const int *idx, const float *grad_out, const int *pcnt_poff,
+                                   const int *plist, float *grad_input, float *grad_position, float *grad_weight,
+                                   void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
