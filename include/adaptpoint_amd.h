@@ -430,7 +430,9 @@ APN_API int apn_sa_wide_grid(int b, int m);          /* workgroups = partial row
  *   qlocal | slot << 8 | mult << 16 | (row 0: queries in the tile) << 24, mult = 0 for padding; then
  *   32 b m ints: every row's neighbour idx[query][slot]; scratch.
  * mode 1: fold the copies of slot 0 of every index row that has the ball-query structure (checked row
- * by row; any other row is kept whole); mode 0: one tile per query, 32 rows of multiplicity 1. */
+ * by row; any other row is kept whole); mode 0: one tile per query, 32 rows of multiplicity 1.
+ * Every index must lie in [0, n), n the support points per cloud: the map stores idx as it comes, and
+ * apn_sa_wide_csr adds it to the cloud's first point without a clamp. */
 APN_API int apn_sa_wide_tilemap_ints(int b, int m);
 APN_API int apn_sa_wide_tilemap(int b, int m, int mode, const int *idx, int *tmap, void *stream);
 /* count tile maps in one pair of launches (the batches of a stacked index stage): map z reads idx + z * b * m * 32
@@ -518,7 +520,9 @@ APN_API int apn_sa_wide_wgrad(int b, int n, int m, int c_mid, int c_out, const f
 /* Inverse map of the tile map (index stage): pcnt_poff int32[2 b n] = for every support point the number of
  * rows that gather it and where its list starts in plist int32[32 b m] (row ids tile * 32 + r, ascending);
  * geo float[4 b n] (may be NULL) = {occurrences, sum of the gathering queries' coordinates} per point; with fidx (b,m) = the
- * point every query is (FPS picks) also fq int32[b n] = the query a point is, or -1 (both may be NULL). */
+ * point every query is (FPS picks) also fq int32[b n] = the query a point is, or -1 (both may be NULL).
+ * Every index of the map's idx must lie in [0, n): a row's neighbour is added to the cloud's first point as it
+ * is (no clamp), and pcnt / plist / geo are written at that address. */
 APN_API int apn_sa_wide_csr(int b, int n, int m, const int *idx, const float *new_xyz, const int *tmap,
                             int *pcnt_poff, int *plist, float *geo, const int *fidx, int *fq, void *stream);
 /* The dense kernels of the path (csrc/sa_wide_dense.hip), one launch each:
@@ -790,7 +794,10 @@ APN_API int apn_spectral_norm_grad_many(int n_layers, const int *rows, const int
  *     (apn_sa_wide_consts2: BatchNorm's dense term dL/dy = D y + E), tmap / pcnt_poff / plist / geo: the NeighbourIndex
  *     of idx (apn_sa_wide_tilemap, apn_sa_wide_csr) -> dU (b,n,c) = dL/dU summed per point in a fixed order (no float
  *     atomics), dT (b,n,c) = dU - sum_k dL/dy[n,k] (dL/dWp = dT^T xyz / radius) and (dp given) dp (b,n,3) =
- *     dT wp / radius.  ysum NULL: eval mode (D = E = 0). */
+ *     dT wp / radius.  ysum NULL: eval mode (D = E = 0).
+ * Indices outside [0, n): pool_fwd brings every idx into its cloud before it follows it (below 0 -> 0, n and above ->
+ * n - 1); the index stage does NOT (apn_sa_wide_tilemap, apn_sa_wide_csr), so pool_bwd's maps must come from an idx
+ * that lies in [0, n) throughout. */
 APN_API int apn_la_pool_rows(int b, int n);
 APN_API int apn_la_pool_fwd(int b, int n, int c, int nsample, float radius, const float *U, const float *xyz,
                             const float *wp, int ldw, const int *idx, const float *gamma, float *ext, void *sel,
