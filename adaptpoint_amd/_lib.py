@@ -191,6 +191,18 @@ SIGNATURES = {
     "apn_po_subtraction_bwd": [_c_int] * 4 + [_c_void_p] * 6,
     "apn_po_aggregation_fwd": [_c_int] * 5 + [_c_void_p] * 6,
     "apn_po_aggregation_bwd": [_c_int] * 5 + [_c_void_p] * 11,
+    "apn_pt_rows": [_c_int] * 3,
+    "apn_pt_mid_rows": [_c_int] * 3,
+    "apn_pt_rel_stats": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 5,
+    "apn_pt_fold": [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p],
+    "apn_pt_colsum_rows": [_c_int],
+    "apn_pt_colsum": [_c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p],
+    "apn_pt_mid": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 7,
+    "apn_pt_attend": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 8,
+    "apn_pt_attend_bwd": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 10,
+    "apn_pt_mid_bwd": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 9,
+    "apn_pt_rel_bwd": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 12 + [_c_int, _c_void_p, _c_void_p],
+    "apn_pt_scatter_bwd": [_c_int] * 3 + [_c_void_p] * 6 + [_c_int, _c_void_p],
 }
 
 _lib = None

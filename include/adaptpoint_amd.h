@@ -1004,6 +1004,68 @@ APN_API int apn_po_aggregation_bwd(int n, int m, int k, int c, int w_c, const fl
                                    const int *plist, float *grad_input, float *grad_position, float *grad_weight,
                                    void *stream);
 
+/* Point Transformer's vector-attention layer behind its q/k/v projection (openpoints/models/backbone/
+ * pointtransformer.py: PointTransformerLayer; csrc/point_transformer.hip).  n stacked rows, k = nsample slots, c channels,
+ * c' = c / 8 attention weights; j = idx[i,s] (n,k) int32, an index outside [0, n) is clamped into it.
+ *   qkv (n rows of pitch ld >= 3c) = [q (c) | k (c) | v (c)], h (n,k,3) = the positional hidden layer,
+ *   wts = W2 (c,3) | b2 (c) | W3^T (c,c') | b3 (c') | W4 (c',c') | b4 (c'),
+ *   bn  = sc1 (c) | sh1 (c) | sc2 (c') | sh2 (c'): the two BatchNorms folded to scale / shift,
+ *   de  = D1 (c) | E1 (c) | D2 (c') | E2 (c'): BatchNorm's dense backward term dL/dx = sc g + D x + E (zeros in eval).
+ *      pr = W2 h + b2 = fma(W2[c,2], h2, fma(W2[c,1], h1, fma(W2[c,0], h0, b2[c])))        r = (k_j - q_i) + pr
+ *      y  = relu(fma(sc1, r, sh1))      t = b3 + sum_c W3[c',c] y[c] (fma, ascending c)     z = relu(fma(sc2, t, sh2))
+ *      l  = b4 + sum_e W4[c',e] z[e]    a = exp(l - max_s l) / sum_s exp(l - max_s l)
+ *      out[i,c] = sum over slots ascending of (v_j[c] + pr[c]) * a[i,s,c mod c']
+ * Forward:
+ *   rows: how many partial rows (workgroups) the strided kernels write: apn_pt_rows(n, k, c) = ceil(n k / 64), at most
+ *     2048 (c <= 64), 1024 (c = 128), 256 (c = 256) or 128 (c = 512); 0 for n == 0 or refused arguments.
+ *   rel_stats: part[rows][2c] (float64) = the workgroups' shares of {sum r, sum r^2} over the n k positions.
+ *   fold: sums[width] (float64) = the rows of part[rows][width] added in a fixed order (16 interleaved ascending runs,
+ *     then the runs ascending); rows <= 2048, width <= 2^20.
+ *   mid: t (n,k,c'); part given: part[apn_pt_mid_rows(n, k, c)][2c'] (float64) = the shares of {sum t, sum t^2}, one row per
+ *     workgroup: a workgroup per tile of 8192 / c positions, at most apn_pt_rows(n, k, c).
+ *   attend: a (n,k,c') and out (n,c).
+ *   colsum: part[apn_pt_colsum_rows(n)][width] (float64) = the workgroups' shares of the column sums of src (n rows of
+ *     pitch ld >= width, 1 <= width <= 1536), each the rows r, r + rows, ... in ascending order; apn_pt_fold adds them: the
+ *     bias gradient of the q/k/v projection.  apn_pt_colsum_rows(n) = ceil(n / 32), at most 1024; 0 outside 0 < n < 2^24.
+ * Backward, go (n,c) = dL/dout; every part is float64 shares of apn_pt_rows(n, k, c) rows, folded by apn_pt_fold:
+ *   attend_bwd: da[i,s,w] = sum over the 8 channels c = w + m c' (m ascending) of go[i,c] (v_j[c] + pr[c]), dl = a (da - sum_s a da),
+ *     g1 (n,k,c') = (W4^T dl) [z > 0]; part[rows][c'c' + 3c'] = {dW4[c',e] = sum dl[c'] z[e], db4 = sum dl, sum g1, sum g1 t}.
+ *   mid_bwd: dt = fma(sc2, g1, fma(D2, t, E2)), g0 = (W3^T dt) [y > 0] (not written);
+ *     part[rows][c'c + c' + 2c] = {dW3[c',c] = sum dt[c'] y[c], db3 = sum dt, sum g0, sum g0 r}.
+ *   rel_bwd: dr (n,k,c) = fma(sc1, g0, fma(D1, r, E1)) -- the one grouped tensor --, dqkv[i, 0:c] = -sum_s dr[i,s] (rows
+ *     of pitch ldg >= 3c), dpr = dr + go[i,c] a[i,s,c mod c'], dh (n,k,3) = W2^T dpr;
+ *     part[rows][4c] = {dW2[c,d] = sum dpr[c] h[d], db2 = sum dpr}.
+ *   scatter_bwd: pcnt_poff / plist = apn_po_csr of idx; dqkv[j, c:2c] = the sum over j's list, in list order, of dr[pos],
+ *     dqkv[j, 2c:3c] = that of go[pos / k, c] a[pos, c mod c']: sequential fp32 adds starting from the first term (an
+ *     empty list gives 0).
+ * c in {32, 64, 128, 256, 512}, 1 <= k <= 32, 0 <= n < 2^24, ld >= 3c, ldg >= 3c, non-null pointers (mid's part may be
+ * NULL): APN_EINVAL otherwise, before any HIP call; n == 0 is a no-op.  One launch per entry: no synchronisation,
+ * allocation, memset or atomic; every output element is written; every sum has a fixed order (a thread's own terms,
+ * then the groups of a workgroup ascending, then apn_pt_fold): two runs give the same bits. */
+APN_API int apn_pt_rows(int n, int k, int c);
+APN_API int apn_pt_mid_rows(int n, int k, int c);
+APN_API int apn_pt_rel_stats(int n, int k, int c, const float *qkv, int ld, const float *h, const int *idx,
+                             const float *wts, double *part, void *stream);
+APN_API int apn_pt_fold(const double *part, int rows, int width, double *sums, void *stream);
+APN_API int apn_pt_colsum_rows(int n);
+APN_API int apn_pt_colsum(int n, int width, const float *src, int ld, double *part, void *stream);
+APN_API int apn_pt_mid(int n, int k, int c, const float *qkv, int ld, const float *h, const int *idx, const float *wts,
+                       const float *bn, float *t, double *part, void *stream);
+APN_API int apn_pt_attend(int n, int k, int c, const float *qkv, int ld, const float *h, const int *idx,
+                          const float *wts, const float *bn, const float *t, float *a, float *out, void *stream);
+APN_API int apn_pt_attend_bwd(int n, int k, int c, const float *qkv, int ld, const float *h, const int *idx,
+                              const float *wts, const float *bn, const float *t, const float *a, const float *go,
+                              float *g1, double *part, void *stream);
+APN_API int apn_pt_mid_bwd(int n, int k, int c, const float *qkv, int ld, const float *h, const int *idx,
+                           const float *wts, const float *bn, const float *de, const float *t, const float *g1,
+                           double *part, void *stream);
+APN_API int apn_pt_rel_bwd(int n, int k, int c, const float *qkv, int ld, const float *h, const int *idx,
+                           const float *wts, const float *bn, const float *de, const float *t, const float *g1,
+                           const float *a, const float *go, float *dr, float *dh, float *dqkv, int ldg, double *part,
+                           void *stream);
+APN_API int apn_pt_scatter_bwd(int n, int k, int c, const float *dr, const float *go, const float *a,
+                               const int *pcnt_poff, const int *plist, float *dqkv, int ldg, void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
