@@ -10,6 +10,7 @@
     chamfer_dist.py                    Chamfer distance (the reference's `chamfer` module and its loss classes)
     emd.py                             earth mover's distance (the reference's `emd_cuda` module and its loss module)
     pointops.py                        the stacked-cloud operators (the reference's `pointops_cuda` module and its Functions)
+    voxel_grid.py                      voxel-grid subsampling of stacked clouds (the reference's host `voxelize`, per-voxel means)
     dp.py      data-parallel plumbing (flat gradient all-reduce, all-reduce SyncBatchNorm)
 
 `pointnet2_batch_cuda.py`, `emd_cuda.py` and `pointops_cuda.py` at the repository root are the drop-in

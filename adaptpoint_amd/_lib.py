@@ -203,6 +203,10 @@ SIGNATURES = {
     "apn_pt_mid_bwd": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 9,
     "apn_pt_rel_bwd": [_c_int] * 3 + [_c_void_p, _c_int] + [_c_void_p] * 12 + [_c_int, _c_void_p, _c_void_p],
     "apn_pt_scatter_bwd": [_c_int] * 3 + [_c_void_p] * 6 + [_c_int, _c_void_p],
+    "apn_vg_scratch_ints": [_c_int],
+    "apn_vg_voxelize": [_c_int] * 3 + [_c_void_p] + [_c_double] * 3 + [_c_void_p] * 9,
+    "apn_vg_mean_fwd": [_c_int] * 3 + [_c_void_p] * 6,
+    "apn_vg_mean_bwd": [_c_int] * 3 + [_c_void_p] * 5,
 }
 
 _lib = None

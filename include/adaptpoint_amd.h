@@ -1066,6 +1066,41 @@ APN_API int apn_pt_rel_bwd(int n, int k, int c, const float *qkv, int ld, const 
 APN_API int apn_pt_scatter_bwd(int n, int k, int c, const float *dr, const float *go, const float *a,
                                const int *pcnt_poff, const int *plist, float *dqkv, int ldg, void *stream);
 
+/* Voxel-grid subsampling of STACKED clouds (csrc/voxel_grid.hip; the reference does it on the host: openpoints/dataset/
+ * data_util.py: voxelize, openpoints/cpp/subsampling): coord (n,3) float32 (is_double = 0) or float64 (is_double = 1),
+ * int32 offset (b) of cumulative END rows as above; row i belongs to the first cloud c with i < offset[c], a row at or
+ * past offset[b-1] to the last one.  Per axis
+ *         cell(i) = floor((double)coord[i] / (double)voxel_size)          (IEEE double division)
+ * A row whose cell does not fit an int32 on some axis, or whose coordinate is not finite, is BAD.  A VOXEL is a set of
+ * rows with equal (cloud, cell); coordinates may be negative.  Every output is a pure function of the inputs: integer
+ * atomics only (compare-and-swap, min, max, add), each where the final value does not depend on the order; two runs give
+ * the same bits.
+ *   voxelize: voxel_of (n): voxels are numbered 0..m-1 in ascending order of their smallest member row (so a cloud's
+ *     voxels are contiguous); idx_sort (n): the rows grouped by voxel number, ascending row inside a voxel (the stable
+ *     argsort of voxel_of); start, count (n each, the first m written): voxel v's rows are idx_sort[start[v] .. start[v] +
+ *     count[v]); new_offset (b): cumulative voxel ends per cloud (an empty cloud repeats the previous end, new_offset[b-1]
+ *     == m); stats (3) = {m, count_max, bad}.  With bad > 0 the bad rows form one voxel of their own and the caller
+ *     rejects the result.  scratch: apn_vg_scratch_ints(n) ints, 16-byte aligned, contents irrelevant (0 for an n the
+ *     entries refuse).  A fixed chain of 9 + 5 ceil(bits(n - 1) / 8) launches, kernel boundaries the only seams: no
+ *     workgroup waits for another, the probe loop of the row table is bounded by the table's size (>= 2n slots: it never
+ *     fills), and the work does not depend on how the rows spread over the voxels.
+ *   mean_fwd: out (m,c): out[v,ch] = (float)((double)s / (double)count[v]), the correctly rounded fp32 quotient, where s
+ *     = the sequential fp32 sum of values[idx_sort[j], ch] (values (n,c)) over j = start[v] .. start[v] + count[v],
+ *     STARTING FROM THE FIRST TERM: ascending row.  One thread per (voxel, channel).
+ *   mean_bwd: grad_values[i,ch] = (float)((double)grad_out[voxel_of[i], ch] / (double)count[voxel_of[i]]): a gather.
+ * b >= 1, 0 <= n < 2^27, 0 <= m <= n, 1 <= c <= 65536, voxel sizes finite and > 0, non-null pointers: APN_EINVAL
+ * otherwise, before any HIP call.  n == 0 (voxelize: m = 0, nothing is written) or m == 0 is a no-op.  No entry
+ * synchronises, allocates or issues a memset; element offsets are 64-bit inside the kernels; indices read from memory
+ * are clamped into range before they address anything. */
+APN_API int apn_vg_scratch_ints(int n);
+APN_API int apn_vg_voxelize(int b, int n, int is_double, const void *coord, double vx, double vy, double vz,
+                            const int *offset, int *scratch, int *voxel_of, int *count, int *start, int *idx_sort,
+                            int *new_offset, int *stats, void *stream);
+APN_API int apn_vg_mean_fwd(int n, int m, int c, const float *values, const int *idx_sort, const int *start,
+                            const int *count, float *out, void *stream);
+APN_API int apn_vg_mean_bwd(int n, int m, int c, const float *grad_out, const int *voxel_of, const int *count,
+                            float *grad_values, void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
