@@ -207,6 +207,13 @@ SIGNATURES = {
     "apn_vg_voxelize": [_c_int] * 3 + [_c_void_p] + [_c_double] * 3 + [_c_void_p] * 9,
     "apn_vg_mean_fwd": [_c_int] * 3 + [_c_void_p] * 6,
     "apn_vg_mean_bwd": [_c_int] * 3 + [_c_void_p] * 5,
+    "apn_rl_moment_rows": [_c_int] * 3,
+    "apn_rl_bwd_rows": [_c_int] * 4,
+    "apn_rl_moments": [_c_int] * 3 + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 3,
+    "apn_rl_fold": [_c_int, _c_void_p, _c_double] + [_c_void_p] * 4 + [_c_float, _c_float, _c_int] + [_c_void_p] * 6,
+    "apn_rl_forward": [_c_int] * 4 + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 4,
+    "apn_rl_backward": [_c_int] * 4 + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 6,
+    "apn_rl_finalize": [_c_int, _c_int, _c_void_p, _c_void_p, _c_double] + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3,
 }
 
 _lib = None

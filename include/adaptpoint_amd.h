@@ -1101,6 +1101,43 @@ APN_API int apn_vg_mean_fwd(int n, int m, int c, const float *values, const int 
 APN_API int apn_vg_mean_bwd(int n, int m, int c, const float *grad_out, const int *voxel_of, const int *count,
                             float *grad_values, void *stream);
 
+/* RandLA-Net's LocalSpatialEncoding + AttentivePooling as one layer (csrc/randla.hip).
+ * coords (b,n,3) float32; idx (b,n,k) int32 and dist (b,n,k) float32 as apn_knn_query returns them for support = query
+ * = coords (idx is clamped into [0, n)); sqrt_dist != 0: the kernels take the root of dist.  Per (point, neighbour) pair
+ * e = [p_n, p_j, p_n - p_j, dist] (10 wide).  Shapes: b >= 0 (0: nothing is launched), n >= 1, 1 <= k <= 32,
+ * b n < 2^24, c in {8, 16, 32, 64, 128}; anything else is APN_EINVAL before a launch.
+ *   moments: mom[65] (float64) = {sum e_i (10), sum e_i e_j for i <= j (55, row-major upper triangle)} over the b n k
+ *     pairs; part[apn_rl_moment_rows(b, n, k)][65] (float64) is the workgroups' shares, added in ascending order.
+ *   fold: w (c,10), bias (c or NULL): the convolution; gamma, beta (c or NULL), eps, momentum: its BatchNorm; count =
+ *     b n k.  training != 0: batch mean = w.mu + bias and biased variance = w^T Sigma w from mom; running_mean /
+ *     running_var (both or neither) take (1 - momentum) old + momentum new, the variance unbiased, and
+ *     *num_batches_tracked (int64, or NULL) grows by one.  training == 0: the running buffers are the statistics (mom may
+ *     be NULL).  wf[11 c + 10] (float32) = W' (c,10), b' (c), mu (10: the encoding's batch mean, zeros when training == 0):
+ *     relu(W' (e - mu) + b') is the layer's hidden value;
+ *     stat[3 c] (float64) = mean | variance | 1 / sqrt(variance + eps) as used.
+ *   forward: at (c,c): at[c2 c + c1] = A_hh[c1][c2], the transposed top-left block of the 2c x 2c score weight.
+ *     pooled (b,c,n): pooled[c1,n] = sum_k softmax_k((A_hh h_k)[c1]) h_k[c1].
+ *   backward: a (c,c) = A_hh, at its transpose, dpooled (b,c,n); part[apn_rl_bwd_rows(b, n, k, c)][c c + 11 c]
+ *     (float32): per workgroup the shares of dA_hh and, per channel, of {sum dy (e - mu)_0..9, sum dy}.
+ *   finalize: rows = apn_rl_bwd_rows(...); sums[c c + 11 c] (float64): scratch, the rows added in ascending order;
+ *     grads[c c + 13 c] (float32) = dA_hh | dgamma | dbeta | dW (c,10) | dbias (dbias is an exact zero when training != 0).  No gradient flows to coords, dist or idx.
+ * Every sum has an order fixed by the shapes: two runs give the same bits.  No atomics, no memset. */
+APN_API int apn_rl_moment_rows(int b, int n, int k);
+APN_API int apn_rl_bwd_rows(int b, int n, int k, int c);
+APN_API int apn_rl_moments(int b, int n, int k, const float *coords, const int *idx, const float *dist, int sqrt_dist,
+                           double *part, double *mom, void *stream);
+APN_API int apn_rl_fold(int c, const double *mom, double count, const float *w, const float *bias, const float *gamma,
+                        const float *beta, float eps, float momentum, int training, float *running_mean,
+                        float *running_var, long long *num_batches_tracked, float *wf, double *stat, void *stream);
+APN_API int apn_rl_forward(int b, int n, int k, int c, const float *coords, const int *idx, const float *dist,
+                           int sqrt_dist, const float *wf, const float *at, float *pooled, void *stream);
+APN_API int apn_rl_backward(int b, int n, int k, int c, const float *coords, const int *idx, const float *dist,
+                            int sqrt_dist, const float *wf, const float *a, const float *at, const float *dpooled,
+                            float *part, void *stream);
+APN_API int apn_rl_finalize(int c, int rows, const float *part, const double *mom, double count, const float *w,
+                            const float *bias, const float *gamma, const double *stat, int training, double *sums,
+                            float *grads, void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
