@@ -9,9 +9,9 @@
 // points at once, a ballot turns the hits into a 64-bit mask, and
 // mbcnt (popcount of the lower lanes) gives every hit its slot in index order
 // -- the order the sequential scan would have produced.  The cloud's xyz is
-// staged once per workgroup into LDS as three planes (x[], y[], z[]), read back
-// with conflict-free ds_read_b32, and reused by every query of the tile; the
-// query's own coordinates are wave-uniform (SGPRs).
+// staged once per workgroup into LDS as three planes (x[], y[], z[]); every wave
+// copies 1024 points of them into registers once and scans those for each of its
+// queries (ball_query_body.h); the query's own coordinates are wave-uniform (SGPRs).
 //
 // Semantics kept bit-exact (ball_query_gpu.cu:29-48): radius2 = radius*radius in
 // float32; strict d2 < radius2 with d2 = fma(dz,dz, fma(dx,dx, dy*dy)) on

@@ -6,18 +6,31 @@
 namespace apn {
 
 constexpr int BQ_CHUNK = 4096;             // support points staged per LDS pass (48 KiB)
-constexpr int BQ_QPW = 4;                  // queries a wave tests each staged point against (8 for full tiles: ball_query.hip)
+constexpr int BQ_QPW = 4;                  // consecutive queries a wave owns (8 for full tiles: ball_query.hip)
+constexpr int BQ_SLOTS = 16;               // register slots of a wave's chunk: lane l, slot s holds point 64 s + l
+constexpr int BQ_REG = 64 * BQ_SLOTS;      // support points a wave holds in registers (48 VGPRs)
+constexpr int BQ_GROUP = 4;                // slots compared before their hits are emitted (the early exit's granularity)
+
+// The value as the compiler cannot see through it: what is derived from it inside a rarely taken block is computed
+// there, and not hoisted out of the query loop as sixteen loop-invariant registers (one per slot).
+__device__ __forceinline__ int opaque_v(int v) { asm volatile("" : "+v"(v)); return v; }
 
 // One workgroup of WAVES waves: tile `bx` of cloud `cloud`; each wave owns queries
-// q0 + wave, q0 + wave + WAVES, ... of the tile.  s_dyn: three coordinate planes of
-// min(n, BQ_CHUNK) floats, then 2 * q_per_block ints.
+// q0 + QPW * wave .. + QPW - 1, then those WAVES * QPW further on, of the tile.  s_dyn: three coordinate
+// planes of min(n, BQ_CHUNK) floats, then 2 * q_per_block ints.
+//
+// A wave copies BQ_REG staged points into registers once and scans them for each of its queries without
+// reading LDS again.  The scan of a query is straight-line: for a group of BQ_GROUP slots the BQ_GROUP
+// hit masks (7 float instructions per slot, the compare writes the mask), THEN, for the non-empty masks in
+// slot order, the slots of the hits (count + mbcnt) and their stores.  Lanes past the end of the cloud
+// hold NaN coordinates: their d2 is NaN and `d2 < radius2` is false for every radius2, so the loop
+// carries no per-lane bounds test.  A group of slots is copied from LDS when the first query reaches it:
+// queries whose balls saturate early never pay for the rest of the chunk.
 template <int WAVES, int QPW = BQ_QPW>
 __device__ __forceinline__ void ball_query_body(
     int n, int m, float radius2, int nsample, int q_per_block, int zero_empty,
     const float *__restrict__ new_xyz, const float *__restrict__ xyz, int *__restrict__ idx,
     int cloud, int bx, float *s_dyn) {
-    // Dynamic LDS: three coordinate planes of `chunk` floats, then per query of
-    // the tile its hit count so far and its first hit.
     const int chunk = min(n, BQ_CHUNK);
     float *sx = s_dyn, *sy = s_dyn + chunk, *sz = s_dyn + 2 * chunk;
     int *s_cnt = reinterpret_cast<int *>(s_dyn + 3 * chunk);
@@ -32,9 +45,22 @@ __device__ __forceinline__ void ball_query_body(
     new_xyz += (size_t)cloud * m * 3;
     idx += (size_t)cloud * m * nsample;
 
+    // Clouds above BQ_REG points: a query's hit count and first hit pass from one register chunk to the
+    // next through LDS.  The same wave owns the query in every chunk, so no barrier orders these.
+    const bool carried = n > BQ_REG;
     int *cnt_of = s_cnt;
     int *first_of = s_cnt + q_per_block;
-    for (int i = tid; i < q_per_block; i += WAVES * 64) { cnt_of[i] = 0; first_of[i] = 0; }
+    if (carried)
+        for (int i = tid; i < q_per_block; i += WAVES * 64) { cnt_of[i] = 0; first_of[i] = 0; }
+
+    // The end of a query's row, by the wave that scanned it: slots the scan never reached repeat the
+    // first hit (ball_query_gpu.cu:41-45).  Rows of empty balls stay untouched, or become zeros.
+    auto finish = [&](int q, int cnt, int first) {
+        if ((cnt == 0 && !zero_empty) || cnt >= nsample) return;
+        int *row = idx + (size_t)q * nsample;
+#pragma nounroll
+        for (int l = cnt + lane; l < nsample; l += 64) row[l] = first;   // first == 0 for an empty ball
+    };
 
     for (int base = 0; base < n; base += BQ_CHUNK) {
         const int len = min(BQ_CHUNK, n - base);
@@ -47,67 +73,85 @@ __device__ __forceinline__ void ball_query_body(
         }
         __syncthreads();
 
-        // A wave takes QPW consecutive queries per pass over the chunk: a point's coordinates are read from LDS
-        // once for all of them (one query per pass spent most of its instructions on the three LDS reads and the
-        // loop; the per-query part -- distance, ballot, slot arithmetic -- and the order of the hits are unchanged)
-        for (int qb = q_begin + wave * QPW; qb < q_end; qb += WAVES * QPW) {
-            int cnt[QPW], first[QPW];
-            float qx[QPW], qy[QPW], qz[QPW];
-            bool open = false;
+        for (int rc = 0; rc < len; rc += BQ_REG) {
+            const int rlen = min(BQ_REG, len - rc);                 // >= 1
+            const bool last = base + rc + BQ_REG >= n;              // the cloud ends in this register chunk
+            const int point0 = base + rc + lane;                    // the point of slot 0
+            float px[BQ_SLOTS], py[BQ_SLOTS], pz[BQ_SLOTS];
 #pragma unroll
-            for (int j = 0; j < QPW; ++j) {
-                const int q = qb + j;
-                const bool in = q < q_end;
-                cnt[j] = in ? __builtin_amdgcn_readfirstlane(cnt_of[q - q_begin]) : nsample;   // wave-uniform
-                first[j] = in ? __builtin_amdgcn_readfirstlane(first_of[q - q_begin]) : 0;
-                const int qc = in ? q : q_begin;
-                qx[j] = new_xyz[qc * 3 + 0];
-                qy[j] = new_xyz[qc * 3 + 1];
-                qz[j] = new_xyz[qc * 3 + 2];
-                open = open || cnt[j] < nsample;
-            }
-            if (!open) continue;
-            for (int k0 = 0; k0 < len; k0 += 64) {
-                const int k = k0 + lane;
-                const bool inside = k < len;
-                const float px = inside ? sx[k] : 0.0f, py = inside ? sy[k] : 0.0f, pz = inside ? sz[k] : 0.0f;
-                bool any_open = false;
-#pragma unroll
-                for (int j = 0; j < QPW; ++j) {
-                    if (cnt[j] >= nsample) continue;              // wave-uniform
-                    const bool hit = inside && dist2(qx[j] - px, qy[j] - py, qz[j] - pz) < radius2;
-                    const unsigned long long mask = __ballot(hit);
-                    if (mask != 0ull) {
-                        if (cnt[j] == 0) first[j] = base + k0 + (int)__builtin_ctzll(mask);
-                        const int slot = cnt[j] + (int)__builtin_amdgcn_mbcnt_hi(
-                                                      (unsigned)(mask >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                        if (hit && slot < nsample) idx[(size_t)(qb + j) * nsample + slot] = base + k;
-                        cnt[j] += (int)__builtin_popcountll(mask);
+            for (int s = 0; s < BQ_SLOTS; ++s) px[s] = py[s] = pz[s] = __builtin_nanf("");
+            int loaded = 0;                                         // groups of slots already in registers (wave-uniform)
+
+#pragma nounroll
+            for (int qb = q_begin + wave * QPW; qb < q_end; qb += WAVES * QPW) {
+                const int qe = min(qb + QPW, q_end);
+                float nx = new_xyz[qb * 3 + 0], ny = new_xyz[qb * 3 + 1], nz = new_xyz[qb * 3 + 2];   // wave-uniform (scalar loads)
+#pragma nounroll
+                for (int q = qb; q < qe; ++q) {
+                    const float qx = nx, qy = ny, qz = nz;
+                    const int qn = min(q + 1, qe - 1);              // the next query's coordinates arrive during this one's scan
+                    nx = new_xyz[qn * 3 + 0]; ny = new_xyz[qn * 3 + 1]; nz = new_xyz[qn * 3 + 2];
+                    int cnt = 0, first = 0;
+                    if (carried) {
+                        cnt = __builtin_amdgcn_readfirstlane(cnt_of[q - q_begin]);
+                        first = __builtin_amdgcn_readfirstlane(first_of[q - q_begin]);
                     }
-                    any_open = any_open || cnt[j] < nsample;
-                }
-                if (!any_open) break;
-            }
-            if (lane == 0) {
+                    if (cnt < nsample) {
+                        int *row = idx + (size_t)q * nsample;
+                        const bool empty = cnt == 0;
+                        int rel = 0;                                // the first hit, counted from the register chunk's start
 #pragma unroll
-                for (int j = 0; j < QPW; ++j)
-                    if (qb + j < q_end) { cnt_of[qb + j - q_begin] = cnt[j]; first_of[qb + j - q_begin] = first[j]; }
+                        for (int g = 0; g < BQ_SLOTS / BQ_GROUP; ++g) {
+                            if (g * BQ_GROUP * 64 >= rlen) break;
+                            if (loaded == g) {                      // the first query to get here fills the group's registers
+#pragma unroll
+                                for (int t = 0; t < BQ_GROUP; ++t) {
+                                    const int s = g * BQ_GROUP + t;
+                                    const int k = 64 * s + opaque_v(lane);
+                                    const int kc = rc + min(k, rlen - 1);
+                                    const float vx = sx[kc], vy = sy[kc], vz = sz[kc];
+                                    if (k < rlen) { px[s] = vx; py[s] = vy; pz[s] = vz; }
+                                }
+                                loaded = g + 1;
+                            }
+                            bool hit[BQ_GROUP];
+                            unsigned long long mask[BQ_GROUP];
+#pragma unroll
+                            for (int t = 0; t < BQ_GROUP; ++t) {
+                                const int s = g * BQ_GROUP + t;
+                                hit[t] = dist2(qx - px[s], qy - py[s], qz - pz[s]) < radius2;
+                                mask[t] = __ballot(hit[t]);
+                            }
+#pragma unroll
+                            for (int t = 0; t < BQ_GROUP; ++t) {
+                                if (mask[t] == 0ull) continue;      // wave-uniform
+                                const int s = g * BQ_GROUP + t;
+                                if (cnt == 0) rel = 64 * s + (int)__builtin_ctzll(mask[t]);   // a select, no branch
+                                const int slot = cnt + (int)__builtin_amdgcn_mbcnt_hi(
+                                                           (unsigned)(mask[t] >> 32),
+                                                           __builtin_amdgcn_mbcnt_lo((unsigned)mask[t], 0u));
+                                if (hit[t] && slot < nsample)       // base pointer + 32-bit byte offset: one store, no 64-bit lane address
+                                    *reinterpret_cast<int *>(reinterpret_cast<char *>(row) + (unsigned)slot * 4u) = opaque_v(point0) + 64 * s;
+                                cnt += (int)__builtin_popcountll(mask[t]);
+                            }
+                            if (cnt >= nsample) break;              // once per group of slots
+                        }
+                        if (empty && cnt > 0) first = base + rc + rel;
+                    }
+                    if (last) {
+                        finish(q, cnt, first);
+                    } else if (lane == 0) {
+                        cnt_of[q - q_begin] = cnt;
+                        first_of[q - q_begin] = first;
+                    }
+                }
             }
         }
     }
 
-    __syncthreads();   // the counts were left by the wave that scanned the query's group of QPW, read below per query
-    // Tail of each row: slots the scan never reached repeat the first hit
-    // (ball_query_gpu.cu:41-45).  Rows of empty balls stay untouched.
-    for (int q = q_begin + wave; q < q_end; q += WAVES) {
-        const int ql = q - q_begin;
-        const int cnt = __builtin_amdgcn_readfirstlane(cnt_of[ql]);
-        if ((cnt == 0 && !zero_empty) || cnt >= nsample) continue;
-        const int first = __builtin_amdgcn_readfirstlane(first_of[ql]);   // 0 for an empty ball
-        int *row = idx + (size_t)q * nsample;
-        for (int l = cnt + lane; l < nsample; l += 64) row[l] = first;
-    }
+    // a cloud without points under the zero-writing contract: every row of the tile is an empty ball
+    if (n == 0)
+        for (int q = q_begin + wave; q < q_end; q += WAVES) finish(q, 0, 0);
 }
 
 
