@@ -214,6 +214,15 @@ SIGNATURES = {
     "apn_rl_forward": [_c_int] * 4 + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 4,
     "apn_rl_backward": [_c_int] * 4 + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 6,
     "apn_rl_finalize": [_c_int, _c_int, _c_void_p, _c_void_p, _c_double] + [_c_void_p] * 4 + [_c_int] + [_c_void_p] * 3,
+    "apn_ag_moment_rows": [_c_int],
+    "apn_ag_point_rows": [_c_int],
+    "apn_ag_moments": [_c_int] * 5 + [_c_void_p] * 5,
+    "apn_ag_fold": [_c_int] * 2 + [_c_void_p] * 3,
+    "apn_ag_combine_fwd": [_c_int] * 5 + [_c_void_p] * 7 + [_c_int] + [_c_void_p] * 4 + [_c_float, _c_int] + [_c_void_p] * 3,
+    "apn_ag_combine_bwd": [_c_int] * 5 + [_c_void_p] * 11,
+    "apn_ag_sigma_bwd": [_c_int] * 5 + [_c_void_p] * 11,
+    "apn_ag_res_relu_max": [_c_int] * 4 + [_c_void_p] * 5,
+    "apn_ag_res_relu_max_grad": [_c_int] * 4 + [_c_void_p] * 6,
 }
 
 _lib = None

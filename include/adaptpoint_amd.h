@@ -1138,6 +1138,61 @@ APN_API int apn_rl_finalize(int c, int rows, const float *part, const double *mo
                             const float *bias, const float *gamma, const double *stat, int training, double *sums,
                             float *grads, void *stream);
 
+/* PointMLP's geometric-affine grouping stage with its first convolution hoisted to the points (csrc/affine_group.hip):
+ * LocalGrouper(normalize="anchor", use_xyz=False) + PreExtraction.transfer's bias-free convolution
+ * (openpoints/models/backbone/pointmlp.py).  Per cloud, with j = idx[s,k] and a = fps_idx[s]:
+ *         d[s,k,:] = x[j,:] - x[a,:],   sigma = unbiased std of the s k c entries of d,   r = 1 / (sigma + 1e-5)
+ *         y[s,k,:] = r (P[j,:] - P[a,:]) + Q[a,:] + c0,    [P | Q] = x [W1 alpha | W2]^T,  c0 = W1 beta
+ * b clouds of n points, s queries of k neighbours; x (b,n,c) ROWS, pq (b,n,2o) rows [P | Q], idx (b,s,k) and
+ * fps_idx (b,s) int32 indices INTO THE CLOUD (every index read is clamped into [0, n)), y (b,o,s k) channels first with
+ * position s k + slot.  Everything fp32 / int32 and contiguous; element offsets are 64-bit inside the kernels.
+ *   moments: part [apn_ag_moment_rows(s)][b][2] = float64 {sum d, sum d^2} of each workgroup's queries (d rounded to
+ *     fp32 as the subtraction gives it, squared and added in float64); apn_ag_fold(rows, 2 b) gives the (b,2) moments.
+ *   fold: out[col] = the sum of part[rows][ncol] (float64) over the rows: ascending inside four equal row ranges, the
+ *     ranges then added in order.
+ *   combine_fwd: r (b) and c0 (o) are INPUT arrays.  v = ((r * (P[j] - P[a])) + Q[a]) + c0, each operation rounded.
+ *     training != 0: y and part are written -- part [apn_pw_conv_tiles(b, s k)][2][o], BatchNorm's partial statistics in
+ *       the layout apn_pw_bn_act folds ({sum, M2 around the tile's own mean} per 128 positions of a cloud).
+ *     training == 0: out = [relu](scale v + shift) from the running statistics (gamma / beta may be null) in the same
+ *       launch; y and stat [4][o] are written when not null (apn_fp_blend_stats's form).
+ *   combine_bwd: gyt = dL/dy as ROWS (b, s k, o) (apn_pw_transpose of the channels-first gradient); the reverse lists of
+ *     idx and of fps_idx are apn_po_csr's on FLAT rows (index + cloud * n; n = b n rows, m = b s queries, k and 1): the
+ *     anchors of a cloud need not be distinct.  With A_i = the sum over i's neighbour list of gyt[pos] and G_i = the sum
+ *     over the queries anchored at i of (sum_k gyt[s,k], ascending k), both in list order in fp32:
+ *         dpq[i] = [ r (A_i - G_i) | G_i ]                                  every element written
+ *         part_dr [apn_ag_point_rows(n)][b]  = float64 shares of  dr[b]  = sum_i <P_i, A_i - G_i>  (= sum <gy, P[j] - P[a]>)
+ *         part_c0 [b apn_ag_point_rows(n)][o] = float64 shares of  dc0[o] = sum_i G_i
+ *     both folded by apn_ag_fold.
+ *   sigma_bwd: kappa (b), mu (b) input arrays;
+ *         dx[i] = kappa (sum over i's neighbour list of ((x_i - x_a) - mu) - sum over the queries anchored at i of
+ *                 sum_k ((x_j - x_i) - mu)),  every element of dx (b,n,c) written.
+ *   res_relu_max: z, h (b,o,s k) -> out (b,o,s) = max_k relu(z + h), sel (b,o,s) uint8 = the slot of the FIRST maximum,
+ *     0 where no sum is positive (out = 0 there).  grad: gz (and gh unless null) (b,o,s k) = g at the kept slot where
+ *     out > 0, zero elsewhere; every element written.
+ * No float atomics: every sum runs in an order fixed by the shapes.  One launch per entry; no synchronisation,
+ * allocation or memset.  1 <= k <= 64, k <= n, b <= 65535, b n < 2^24, b s < 2^24 (res_relu_max: o <= 65535,
+ * b o s < 2^31), non-negative sizes, non-null pointers: APN_EINVAL otherwise, before any HIP call; a zero-sized problem is
+ * a no-op. */
+APN_API int apn_ag_moment_rows(int s);
+APN_API int apn_ag_point_rows(int n);
+APN_API int apn_ag_moments(int b, int n, int s, int k, int c, const float *x, const int *idx, const int *fps_idx,
+                           double *part, void *stream);
+APN_API int apn_ag_fold(int rows, int ncol, const double *part, double *out, void *stream);
+APN_API int apn_ag_combine_fwd(int b, int n, int s, int k, int o, const float *pq, const int *idx, const int *fps_idx,
+                               const float *r, const float *c0, float *y, float *part, int training, const float *gamma,
+                               const float *beta, const float *run_mean, const float *run_var, float eps, int relu,
+                               float *stat, float *out, void *stream);
+APN_API int apn_ag_combine_bwd(int b, int n, int s, int k, int o, const float *gyt, const float *r, const float *pq,
+                               const int *pcnt_poff_i, const int *plist_i, const int *pcnt_poff_a, const int *plist_a,
+                               float *dpq, double *part_dr, double *part_c0, void *stream);
+APN_API int apn_ag_sigma_bwd(int b, int n, int s, int k, int c, const float *x, const int *idx, const int *fps_idx,
+                             const float *kappa, const float *mu, const int *pcnt_poff_i, const int *plist_i,
+                             const int *pcnt_poff_a, const int *plist_a, float *dx, void *stream);
+APN_API int apn_ag_res_relu_max(int b, int o, int s, int k, const float *z, const float *h, float *out, void *sel,
+                                void *stream);
+APN_API int apn_ag_res_relu_max_grad(int b, int o, int s, int k, const float *g, const float *out, const void *sel,
+                                     float *gz, float *gh, void *stream);
+
 /* Tuning / diagnostic entry, NOT part of the reference boundary: apn_furthest_point_sampling
  * with the number of wavefronts that cooperate on one cloud (1, 2, 4, 8 or 16; 0 = the built-in
  * heuristic) and the step algorithm (0 = one LDS 64-bit atomic max per step for n <= 4096: what the operator
