@@ -82,6 +82,9 @@ SIGNATURES = {
     "apn_attention_prep": [_c_int] * 3 + [_c_void_p] * 4 + [_c_int, _c_void_p],
     "apn_attention_fwd": [_c_int] * 3 + [_c_void_p] * 4,
     "apn_attention_bwd": [_c_int] * 3 + [_c_void_p] * 9,
+    "apn_token_attention_max_tokens": [],
+    "apn_token_attention_fwd": [_c_int] * 3 + [_c_void_p] * 4,
+    "apn_token_attention_bwd": [_c_int] * 3 + [_c_void_p] * 7,
     "apn_pointset_group_rows": [_c_int] * 3,
     "apn_pointset_group_max": [_c_int] * 5 + [_c_void_p] * 8,
     "apn_pointset_group_max_grad": [_c_int] * 5 + [_c_void_p] * 9,

@@ -414,6 +414,24 @@ APN_API int apn_attention_bwd(int b, int m, int heads, const void *images, const
                               const float *lse, const float *g_out, void *scratch, float *dq,
                               float *dk, float *dv, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Token attention at head_dim 64 (csrc/token_attention.hip): PointViT's `Attention`
+ * (openpoints/models/backbone/pointvit.py), out = softmax(q k^T / 8) v per (cloud, head), for ANY t >= 1, without
+ * the (B,H,T,T) score tensor in either direction.
+ *   qkv   (B, t, [3][heads][64]) f32, as nn.Linear(dim, 3 dim) leaves it
+ *   out   (B, t, heads*64) f32;  lse (B, heads, t) f32, the log2-domain log-sum-exp of every query
+ *   bwd:  g_out (B, t, heads*64) = dL/d out -> dqkv (B, t, [3][heads][64]), every element written;
+ *         delta: scratch of b*heads*t floats (rowsum(g_out * out), written first)
+ * No atomics: two calls give the same bits, and a (cloud, head)'s results do not depend on b, heads or its neighbours.
+ * 0 < b, heads <= 65535 (grid dimensions), 0 < t <= apn_token_attention_max_tokens() = 2^24 and
+ * b*t*heads < 16 * (2^31 - 1).  qkv, out, g_out and dqkv are reached by 16-byte vector accesses and must be 16-byte
+ * aligned: APN_EINVAL otherwise, before any launch.
+ * ------------------------------------------------------------------------ */
+APN_API int apn_token_attention_max_tokens(void);
+APN_API int apn_token_attention_fwd(int b, int t, int heads, const float *qkv, float *out, float *lse, void *stream);
+APN_API int apn_token_attention_bwd(int b, int t, int heads, const float *qkv, const float *out, const float *lse,
+                                    const float *g_out, float *delta, float *dqkv, void *stream);
+
 /* ---- width-generic fused grouped MLP (csrc/sa_wide.hip): C_mid = H in {32,64,128,256}, C_out = 2H,
  * K = 32.  conv1 is hoisted to the points by the caller: U (B,N,H) = W1f f + W1p p / r per point,
  * V (B,M,H) = W1p new_p / r per query, so that y1[q,k] = U[idx[q,k]] - V[q]
