@@ -85,6 +85,12 @@ SIGNATURES = {
     "apn_token_attention_max_tokens": [],
     "apn_token_attention_fwd": [_c_int] * 3 + [_c_void_p] * 4,
     "apn_token_attention_bwd": [_c_int] * 3 + [_c_void_p] * 7,
+    "apn_depth_views_max_splats": [],
+    "apn_depth_views_max_pixels": [],
+    "apn_depth_views_max_views": [],
+    "apn_depth_views_max_images": [],
+    "apn_depth_views_fwd": [_c_int] * 7 + [_c_void_p] * 6,
+    "apn_depth_views_bwd": [_c_int] * 7 + [_c_void_p] * 8,
     "apn_pointset_group_rows": [_c_int] * 3,
     "apn_pointset_group_max": [_c_int] * 5 + [_c_void_p] * 8,
     "apn_pointset_group_max_grad": [_c_int] * 5 + [_c_void_p] * 9,

@@ -432,6 +432,31 @@ APN_API int apn_token_attention_fwd(int b, int t, int heads, const float *qkv, f
 APN_API int apn_token_attention_bwd(int b, int t, int heads, const float *qkv, const float *out, const float *lse,
                                     const float *g_out, float *delta, float *dqkv, void *stream);
 
+/* ------------------------------------------------------------------------
+ * SimpleView's six-view depth rasteriser (csrc/depth_views.hip): `PCViews.get_img` -> `points2depth` -> `distribute`
+ * (openpoints/models/backbone/simpleview_util.py) in one forward and one backward launch.
+ *   points (b,n,3) f32; rot (views,3,3), trans (views,3): q = p R_v - t_v (fp32, summed left to right, no fma);
+ *   rot == NULL: the points are camera-frame already and views must be 1.
+ *   img, sw (b*views, h, w): image b*views + v is cloud b under view v.  Per pixel, in ascending (point, i, j) order of
+ *   the sx*sy splats of every point: sw = sum w, sv = sum z w with w = 1 / (z + 1e-12f); img = sv / (sw + (sw == 0)).
+ *   Every element of img and sw is written (nothing has to arrive zeroed); no float atomic, no memset, no scratch: two
+ *   calls give the same bits.  Non-finite coordinates contribute nothing.
+ *   bwd: g_img (b*views,h,w) = dL/d img, img and sw as the forward left them -> dpoints (b,n,3), every element
+ *   written; the gradient flows through the depth only (the pixel coordinates pass through ceil).
+ * sx, sy in {1,2,4}; n*sx*sy <= apn_depth_views_max_splats() = 16384, h*w <= apn_depth_views_max_pixels() = 65536,
+ * views <= apn_depth_views_max_views() = 64, b*views <= apn_depth_views_max_images() = 2^22 - 1 (workgroups of 1024
+ * threads: the grid stays below 2^32 threads), b*n < 2^31: APN_EINVAL otherwise, before any launch.
+ * ------------------------------------------------------------------------ */
+APN_API int apn_depth_views_max_splats(void);
+APN_API int apn_depth_views_max_pixels(void);
+APN_API int apn_depth_views_max_views(void);
+APN_API int apn_depth_views_max_images(void);
+APN_API int apn_depth_views_fwd(int b, int n, int views, int h, int w, int sx, int sy, const float *points,
+                                const float *rot, const float *trans, float *img, float *sw, void *stream);
+APN_API int apn_depth_views_bwd(int b, int n, int views, int h, int w, int sx, int sy, const float *points,
+                                const float *rot, const float *trans, const float *g_img, const float *img,
+                                const float *sw, float *dpoints, void *stream);
+
 /* ---- width-generic fused grouped MLP (csrc/sa_wide.hip): C_mid = H in {32,64,128,256}, C_out = 2H,
  * K = 32.  conv1 is hoisted to the points by the caller: U (B,N,H) = W1f f + W1p p / r per point,
  * V (B,M,H) = W1p new_p / r per query, so that y1[q,k] = U[idx[q,k]] - V[q]
