@@ -25,7 +25,7 @@ Neither the grouped (B,S,K,C) tensor, nor its difference, its normalised and aff
               dL/dx += [dP | dQ] [Wa ; W2],  d[Wa ; W2] = sum [dP | dQ]^T x           apn_pw_contract (x2)
 
 The chain from Wa and c0 to W, alpha and beta is three small elementwise products and two column sums in the backward
-pass.  `affine_group_bn_act` adds the layer's BatchNorm (+ ReLU): apn_pw_bn_act on the partial rows in training mode, the
+pass.  `affine_group_bn_act` adds the layer's BatchNorm (+ ReLU): `batchnorm.bn_act` on the partial rows in training mode, the
 combine launch's own eval form (running statistics, one launch, no y) otherwise.  Also here: `bn_act` and `res_relu_max` (the tail of a PreExtraction: add + ReLU + max over K).
 Gradients are bit-identical from run to run: no float atomics anywhere.  There is no CPU fallback.
 """
@@ -33,7 +33,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, batchnorm
 from .fused import _call, _ptr
 
 K_MAX = 64
@@ -163,14 +163,7 @@ class _AffineGroupLinear(torch.autograd.Function):
         g_gamma = g_bias = None
         if ctx.eval_cfg is not None:
             # gy arrived as dL/d out: through the eval-mode BatchNorm (+ ReLU) first
-            relu, has_gamma, has_bias = ctx.eval_cfg
-            y, stat = ctx.saved_tensors[9:]
-            part_b = torch.empty(lib.apn_pw_bn_act_grad_splits(B, O), 2, O, device=dev)
-            g_out, gy = gy, torch.empty(B, O, S * K, device=dev)
-            ggb = torch.empty(2, O, device=dev)
-            _call("apn_pw_bn_act_grad", dev, B, O, S * K, g_out.data_ptr(), y.data_ptr(), stat.data_ptr(), 0, int(relu),
-                  part_b.data_ptr(), gy.data_ptr(), ggb[0].data_ptr(), ggb[1].data_ptr())
-            g_gamma, g_bias = (ggb[0] if has_gamma else None), (ggb[1] if has_bias else None)
+            gy, g_gamma, g_bias = batchnorm.bn_act_grad(gy, *ctx.saved_tensors[9:], False, *ctx.eval_cfg)
         gyt = torch.empty(B, S * K, O, device=dev)
         _call("apn_pw_transpose", dev, B, O, S * K, gy.data_ptr(), gyt.data_ptr())
         rows = lib.apn_ag_point_rows(N)
@@ -244,54 +237,16 @@ def affine_group_bn_act(x, graph, alpha, beta, weight, bn, relu=True):
     training mode the combine launch leaves BatchNorm's partial rows and apn_pw_bn_act follows (running buffers
     updated); in eval mode the combine launch applies the running statistics itself: one launch, y not written unless a
     gradient is wanted."""
-    training = bn.training or not bn.track_running_stats
-    if training:
+    if batchnorm.mode(bn)[0]:
         y, part = affine_group_linear(x, graph, alpha, beta, weight)
         return bn_act(y, part, bn, relu)
     _check_inputs(x, graph, alpha, beta, weight)
     return _AffineGroupLinear.apply(x.float(), weight, alpha, beta, graph, bn, relu, bn.weight, bn.bias)[0]
 
 
-class _BNAct(torch.autograd.Function):
-    """[relu](bn(y)) for y (B,C,N) whose partial rows exist already: `pointwise._ConvBNAct` without its convolution."""
-
-    @staticmethod
-    def forward(ctx, y, part, gamma, beta, bn, relu):
-        dev = y.device
-        y = y.contiguous()
-        B, C, N = y.shape
-        training = bn.training or not bn.track_running_stats
-        tiles = _lib.load().apn_pw_conv_tiles(B, N)
-        out = torch.empty_like(y)
-        stat = torch.empty(4, C, device=dev)
-        track = bn.track_running_stats and bn.running_mean is not None
-        _call("apn_pw_bn_act", dev, B, C, N, y.data_ptr(), part.data_ptr() if training else None, tiles, _ptr(gamma),
-              _ptr(beta), float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.0), int(training), int(relu),
-              bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-              bn.num_batches_tracked.data_ptr() if (track and training and bn.num_batches_tracked is not None) else None,
-              stat.data_ptr(), out.data_ptr())
-        ctx.save_for_backward(y, stat)
-        ctx.cfg = (training, relu, gamma is not None, beta is not None)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        y, stat = ctx.saved_tensors
-        training, relu, has_gamma, has_beta = ctx.cfg
-        dev = y.device
-        B, C, N = y.shape
-        g = g.contiguous()
-        part_b = torch.empty(_lib.load().apn_pw_bn_act_grad_splits(B, C), 2, C, device=dev)
-        gy = torch.empty_like(y)
-        ggb = torch.empty(2, C, device=dev)
-        _call("apn_pw_bn_act_grad", dev, B, C, N, g.data_ptr(), y.data_ptr(), stat.data_ptr(), int(training), int(relu),
-              part_b.data_ptr(), gy.data_ptr(), ggb[0].data_ptr(), ggb[1].data_ptr())
-        return gy, None, (ggb[0] if has_gamma else None), (ggb[1] if has_beta else None), None, None
-
-
 def bn_act(y, part, bn, relu=True):
     """[relu](bn(y)) for y (B,C,N) and its partial rows `part` as `affine_group_linear` returns them."""
-    return _BNAct.apply(y, part, bn.weight, bn.bias, bn, relu)
+    return batchnorm.BNAct.apply(y, part, bn.weight, bn.bias, bn, relu)
 
 
 class _ResReluMax(torch.autograd.Function):

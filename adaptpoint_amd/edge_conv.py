@@ -13,10 +13,10 @@ Neither the (B,2C,N,K) nor the (B,H,N,K) tensor of the composed path exists, for
 
     index     the reverse-neighbour lists of idx (a function of idx alone, built once per graph)   apn_ec_csr
     forward   [u | v] = x^T [Wa - Wb ; Wb]^T                              the contraction kernel (apn_pw_contract)
-              ext, sel, ysum, BatchNorm's sums                            apn_ec_pool_fwd (+ apn_la_stats_fold)
-              pack = BatchNorm's fold (running buffers updated)           apn_sa_bn_fold
+              ext, sel, ysum, BatchNorm's partial sums                    apn_ec_pool_fwd
+              pack = BatchNorm's fold (running buffers updated)           batchnorm.pooled_stats_pack
               out = act(scale ext + shift) [+ residual], channels first   apn_ec_out_res
-    backward  gsel = g act' scale, {sum g act', sum g act' yhat}          apn_ec_bwd_prep_act, apn_sa_wide_consts2
+    backward  gsel = g act' scale, {sum g act', sum g act' yhat}          apn_ec_bwd_prep_act, batchnorm.dense_terms
               [du | dv] per point through the reverse lists               apn_ec_pool_bwd   (no float atomics)
               dL/dx = [Wa - Wb ; Wb]^T [du | dv]^T, dL/dW from [du | dv]^T x^T    the contraction kernel
 
@@ -32,7 +32,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib, pointwise
+from . import _lib, batchnorm, pointwise
 from . import fused as _fz
 from .fused import _call
 
@@ -88,7 +88,7 @@ class _EdgeConv(torch.autograd.Function):
         B, C, N = x.shape
         H = w.shape[0]
         K = graph.idx.shape[2]
-        training = bn.training or not bn.track_running_stats
+        training = batchnorm.mode(bn)[0]
         f32 = dict(dtype=torch.float32, device=dev)
         lib = _lib.load()
         with torch.no_grad():
@@ -100,20 +100,12 @@ class _EdgeConv(torch.autograd.Function):
             ext = torch.empty(B, N, H, **f32)
             sel = torch.empty(B, N, H, dtype=torch.uint8, device=dev)
             count = float(B * N * K)
-            ysum = part = sums = None
-            if training:
-                rows = lib.apn_ec_pool_rows(B, N)
-                ysum = torch.empty(B, N, H, **f32)
-                part = torch.empty(rows, 2 * H, dtype=torch.float64, device=dev)
+            rows = lib.apn_ec_pool_rows(B, N) if training else 0
+            ysum = torch.empty(B, N, H, **f32) if training else None
+            part = torch.empty(rows, 2 * H, dtype=torch.float64, device=dev) if training else None
             _call("apn_ec_pool_fwd", dev, B, N, H, K, UV.data_ptr(), 2 * H, graph.idx.data_ptr(), _fz._ptr(gamma),
                   ext.data_ptr(), sel.data_ptr(), _fz._ptr(ysum), _fz._ptr(part))
-            if training:
-                sums = torch.empty(2 * H + 2, dtype=torch.float64, device=dev)
-                _call("apn_la_stats_fold", dev, part.data_ptr(), rows, H, count, sums.data_ptr())
-            a = _fz._bn_args(bn)      # (gamma, beta, running_mean, running_var, nbt, eps, momentum, training)
-            pack = torch.empty(4 * H, **f32)
-            _call("apn_sa_bn_fold", dev, None, 0, _fz._ptr(sums), H, count, a[0], a[1], a[5], a[6], a[2], a[3], a[4],
-                  1 if training else 0, pack.data_ptr(), None, 0, None)
+            pack = batchnorm.pooled_stats_pack(part, rows, H, count, bn, training, sync=False)
             out = torch.empty(B, H, N, **f32)
             r = x if res_is_x else res
             if r is not None and (r.shape != out.shape or r.dtype != torch.float32 or r.device != dev):
@@ -148,10 +140,7 @@ class _EdgeConv(torch.autograd.Function):
         gs = g.stride()
         _call("apn_ec_bwd_prep_act", dev, B, N, H, g.data_ptr(), gs[0], gs[1], gs[2], ext.data_ptr(), pack.data_ptr(),
               slope, gsel.data_ptr(), partS.data_ptr())
-        small = torch.empty(4 * H, **f32)
-        de, g_gamma, g_beta = small[:2 * H], small[2 * H:3 * H], small[3 * H:]
-        _call("apn_sa_wide_consts2", dev, partS.data_ptr(), prow, None, H, pack.data_ptr(), count, 1 if training else 0,
-              de.data_ptr(), g_gamma.data_ptr(), g_beta.data_ptr())
+        de, g_gamma, g_beta = batchnorm.dense_terms(partS, prow, H, pack, count, training)
         g_x = g_w = None
         if need_x or need_w:
             dUV = torch.empty(B, N, 2 * H, **f32)

@@ -69,10 +69,6 @@ def _dims(xyz1, xyz2):
     return xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 @torch.no_grad()
 def emd_ratios(xyz1, xyz2):
     """-> (ratio_l (B,10,n), ratio_r (B,10,m)): the iteration; level 0 is the reference's j = 7, level 9 its j = -2."""
@@ -118,7 +114,7 @@ def _sources(what, xyz1, xyz2, match, ratios):
 @torch.no_grad()
 def cost(xyz1, xyz2, match=None, ratios=None):
     """-> cost (B,) = sum_{k,l} d[l,k] match[l,k], `match` read from memory or recomputed from `ratios` = (ratio_l, ratio_r)."""
-    from .fused import _call
+    from .fused import _call, _ptr
     named, shapes = _sources("cost", xyz1, xyz2, match, ratios)
     _check("cost", (("xyz1", xyz1), ("xyz2", xyz2), *named), shapes)
     B, n, m = _dims(xyz1, xyz2)
@@ -134,7 +130,7 @@ def cost(xyz1, xyz2, match=None, ratios=None):
 @torch.no_grad()
 def cost_grad(grad_cost, xyz1, xyz2, match=None, ratios=None):
     """-> (grad1 (B,n,3), grad2 (B,m,3)) of sum(grad_cost * cost), `match` held fixed and taken as in `cost`."""
-    from .fused import _call
+    from .fused import _call, _ptr
     named, shapes = _sources("cost_grad", xyz1, xyz2, match, ratios)
     _check("cost_grad", (("xyz1", xyz1), ("xyz2", xyz2), ("grad_cost", grad_cost), *named),
            (("grad_cost", grad_cost, (xyz1.shape[0],)), *shapes))

@@ -32,6 +32,8 @@ import torch.nn as nn
 
 from . import _lib
 from . import ops as _ops
+from . import batchnorm
+from .batchnorm import ptr as _ptr       # (tests and scripts import the name from here)
 
 C_IN, C_MID, C_OUT, K_NS = 32, 32, 64, 32
 # The register-resident passes run over the distinct-hit tile map of the index stage (fused_wide.tile_map): 3.7x fewer
@@ -115,10 +117,6 @@ class _Launcher:
         _call(name, self.dev, *args, stream=self.stream)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 # Testing hook: run the phased SyncBatchNorm path (reduce rows -> all_reduce -> consumer with
 # sums) even when there is a single rank, so that it can be validated on one GPU.
 FORCE_PHASED = False
@@ -169,20 +167,6 @@ def _all_reduce_acc(call, acc, ncol, count, dev):
     call("apn_sa_reduce_acc", acc.data_ptr(), ncol, float(count), sums.data_ptr())
     _allreduce_sum_(sums)
     return sums
-
-
-def _bn_args(bn):
-    """(gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, training)."""
-    training = bn.training or not bn.track_running_stats
-    track = bn.track_running_stats
-    if bn.momentum is None:
-        raise RuntimeError("fused set abstraction: BatchNorm(momentum=None) is not covered "
-                           "(fused.supported() routes it to the unfused path)")
-    mom = bn.momentum
-    return (_ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean) if track else None,
-            _ptr(bn.running_var) if track else None,
-            _ptr(bn.num_batches_tracked) if (track and bn.training) else None,
-            float(bn.eps), float(mom), 1 if training else 0)
 
 
 def _mat(w, rows, cols):
@@ -247,8 +231,8 @@ class _Forward:
         if want_backward:
             self.zviews, self.zbuf = _carve(dev, self.zsizes)
         zptr, zfl = _ptr(self.zbuf), (self.zbuf.numel() if self.zbuf is not None else 0)
-        bn1a, bn2a = _bn_args(bn1), _bn_args(bn2)
-        self.train1, self.train2 = bool(bn1a[7]), bool(bn2a[7])
+        bn1a, bn2a = batchnorm.args(bn1), batchnorm.args(bn2)
+        self.train1, self.train2 = bool(bn1a.training), bool(bn2a.training)
 
         def run(phases, sums1=None, sums2=None):
             if PER_KERNEL_LAUNCH:
@@ -368,11 +352,11 @@ def _forward_per_kernel(call, phases, prec, B, N, M, radius, p, new_p, f, idx, f
     lib = _lib.load()
     if phases & 1:
         call("apn_sa_prep_stats", B, N, f.data_ptr(), geo.data_ptr(), dd.data_ptr(), w1.data_ptr(), prec,
-             bn1a[7], v["ft"].data_ptr(), v["part1"].data_ptr(), v["acc2"].data_ptr(), lib.apn_sa_acc_words(128))
+             bn1a.training, v["ft"].data_ptr(), v["part1"].data_ptr(), v["acc2"].data_ptr(), lib.apn_sa_acc_words(128))
     if phases & 2:
         call("apn_sa_fwd_main", B, N, M, prec, radius, p.data_ptr(), new_p.data_ptr(), v["ft"].data_ptr(),
              idx.data_ptr(), _ptr(tmap), w1.data_ptr(), w2.data_ptr(), *bn1a, count, v["part1"].data_ptr(), rows1,
-             _ptr(sums1), v["pack1"].data_ptr(), bn2a[0], v["ysel"].data_ptr(), v["ksel"].data_ptr(),
+             _ptr(sums1), v["pack1"].data_ptr(), bn2a.gamma, v["ysel"].data_ptr(), v["ksel"].data_ptr(),
              v["acc2"].data_ptr())
     if phases & 4:
         call("apn_sa_fwd_out", B, N, M, v["ysel"].data_ptr(), v["acc2"].data_ptr(), _ptr(sums2), *bn2a, count,

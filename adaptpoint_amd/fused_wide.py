@@ -21,7 +21,7 @@ gradients of gamma/beta reported as global / world -- see adaptpoint_amd.fused).
 """
 import torch
 
-from . import _lib, pointwise
+from . import _lib, batchnorm, pointwise
 from . import fused as _fz
 from .fused import _call
 
@@ -79,23 +79,22 @@ def _colsum(rows2d):
     return out
 
 
+def _reduced(part, count):
+    """SyncBatchNorm's exchange: the float64 column sums of the partial rows with {count, 1} appended, all-reduced over
+    ranks -> {global sums, global count, world size}."""
+    dev = part.device
+    sums = torch.cat([_colsum(part), torch.full((1,), float(count), dtype=torch.float64, device=dev),
+                      torch.ones(1, dtype=torch.float64, device=dev)])
+    _fz._allreduce_sum_(sums)
+    return sums
+
+
 def _bn_pack(part, rows, C, count, bn, dev, training, sync, sgn_from=None, sgn_c=0):
-    """BatchNorm fold by the extension's `apn_sa_bn_fold` (csrc/sa_glue.hip): the partial rows
-    {sum[C], sumsq[C]} -> pack {scale, shift, mean, invstd}[C] (float32, (4C,)), running buffers and
-    num_batches_tracked updated as torch.nn.BatchNorm does; with `sync` the float64 sums, the position
-    count and a 1 are all-reduced over ranks first.  Rider: sgn (sign of another BatchNorm's gamma)."""
-    pack = torch.empty(4 * C, dtype=torch.float32, device=dev)
-    sgn = torch.empty(sgn_c, dtype=torch.float32, device=dev) if sgn_c else None
-    sums = None
+    """(pack, sgn) of `batchnorm.fold` from the partial rows {sum[C], sumsq[C]}; with `sync` from their exchange over
+    ranks (`_reduced`)."""
     if training and sync:
-        sums = torch.cat([_colsum(part), torch.full((1,), float(count), dtype=torch.float64, device=dev),
-                          torch.ones(1, dtype=torch.float64, device=dev)])
-        _fz._allreduce_sum_(sums)
-    args = _fz._bn_args(bn)      # (gamma, beta, running_mean, running_var, nbt, eps, momentum, training)
-    _call("apn_sa_bn_fold", dev, _fz._ptr(part) if (training and sums is None) else None, rows, _fz._ptr(sums), C,
-          float(count), args[0], args[1], args[5], args[6], args[2], args[3], args[4], 1 if training else 0,
-          pack.data_ptr(), _fz._ptr(sgn_from), sgn_c, _fz._ptr(sgn))
-    return pack, sgn, sums
+        return batchnorm.fold(_reduced(part, count), rows, C, count, bn, training, dev, True, sgn_from, sgn_c)
+    return batchnorm.fold(part, rows, C, count, bn, training, dev, False, sgn_from, sgn_c)
 
 
 def _image(src0, k0, trans0, src1, kd, nc, ct):
@@ -198,10 +197,6 @@ def neighbour_index(idx, new_p, n_points, fold=True, fidx=None, out=None):
     return out
 
 
-def _training(bn):
-    return bn.training or not bn.track_running_stats
-
-
 def lean(C, H):
     """Shapes whose dense products (conv1 at the points, Qm, dL/df, dL/dW1) run in the path's own fused
     kernels (csrc/sa_wide_dense.hip); wider ones hand them to library GEMMs."""
@@ -224,6 +219,7 @@ class _WideBlock(torch.autograd.Function):
         assert ws is None or (fusedd and nbr.fq is not None)
         sync = sync_bn and (_fz._world(True) > 1 or _fz.FORCE_PHASED)
         f32 = dict(dtype=torch.float32, device=dev)
+        tr1, tr2 = batchnorm.mode(bn1)[0], batchnorm.mode(bn2)[0]
         with torch.no_grad():
             W1 = w1.detach().reshape(H, C + 3).contiguous()
             W2 = w2.detach().reshape(O, H).contiguous()
@@ -239,7 +235,7 @@ class _WideBlock(torch.autograd.Function):
                 fs = torch.empty(B, M, C, **f32) if Ws is not None else None
                 # BatchNorm-1's batch statistics come out of the same launch (per-point / per-query terms weighted
                 # by the index stage's occurrence counts: no pass over the positions)
-                if _training(bn1) and K_NS == 32:
+                if tr1 and K_NS == 32:
                     rows1 = _lib.load().apn_sa_wide_fwd_prep_rows(B, N, M)
                     part1 = torch.empty(rows1, 2 * H, **f32)
                 _call("apn_sa_wide_fwd_prep", dev, B, C, N, M, H, O, float(radius), f.data_ptr(), p.data_ptr(),
@@ -257,20 +253,19 @@ class _WideBlock(torch.autograd.Function):
                 w2img = _image(W2, H, True, None, H, O, min(4, O // 32))          # W2^T (H x O)
             grid = _lib.load().apn_sa_wide_grid(B, M)
             count = float(B * M * K_NS)
-            tr1, tr2 = _training(bn1), _training(bn2)
             if tr1 and part1 is None:
                 rows1 = grid
                 part1 = torch.empty(grid, 2 * H, **f32)
                 _call("apn_sa_wide_stats1", dev, B, N, M, H, U.data_ptr(), V.data_ptr(), idx.data_ptr(),
                       tmap.data_ptr(), part1.data_ptr())
-            pack1, sgn2, _ = _bn_pack(part1, rows1, H, count, bn1, dev, tr1, sync, sgn_from=g2, sgn_c=O)
+            pack1, sgn2 = _bn_pack(part1, rows1, H, count, bn1, dev, tr1, sync, sgn_from=g2, sgn_c=O)
             ysel = torch.empty(B, M, O, **f32)
             ksel = torch.empty(B, M, O, dtype=torch.uint8, device=dev)
             part2 = torch.empty(grid, 2 * O, **f32)
             _call("apn_sa_wide_fwd_main", dev, B, N, M, H, O, U.data_ptr(), V.data_ptr(), idx.data_ptr(),
                   tmap.data_ptr(), w2img.data_ptr(), pack1.data_ptr(), sgn2.data_ptr(), ysel.data_ptr(), ksel.data_ptr(),
                   part2.data_ptr())
-            pack2, _, _ = _bn_pack(part2 if tr2 else None, grid, O, count, bn2, dev, tr2, sync)
+            pack2, _ = _bn_pack(part2 if tr2 else None, grid, O, count, bn2, dev, tr2, sync)
             out = torch.empty(B, O, M, **f32)
             _call("apn_sa_wide_out", dev, B, M, O, ysel.data_ptr(), pack2.data_ptr(), C,
                   _fz._ptr(fs if Ws is not None else None), _fz._ptr(Ws),
@@ -301,12 +296,6 @@ class _WideBlock(torch.autograd.Function):
             g = g.float()
         f32 = dict(dtype=torch.float32, device=dev)
 
-        def reduced(part):
-            """SyncBatchNorm: the rows summed, with {count, 1} appended, all-reduced over ranks."""
-            v = torch.cat([_colsum(part), torch.full((1,), count, dtype=torch.float64, device=dev),
-                           torch.ones(1, dtype=torch.float64, device=dev)])
-            _fz._allreduce_sum_(v)
-            return v
         # the upstream gradient (through the block's ReLU) in query-major layout, BatchNorm-2's row sums
         prow = lib.apn_sa_wide_bwd_prep_rows(B, M)
         goa = torch.empty(B, M, O, **f32)
@@ -324,7 +313,7 @@ class _WideBlock(torch.autograd.Function):
         cabc = small[o:o + 3 * H]; o += 3 * H
         g_gamma1 = small[o:o + H]; o += H
         g_beta1 = small[o:o + H]
-        sS = reduced(partS) if sync else None
+        sS = _reduced(partS, count) if sync else None
         if fusedd:
             # BatchNorm-2 backward constants, Qm = W2^T diag(D2) W2, evec = E2 W2, image of [W2 ; Qm]: one launch
             ctz = min(4, H // 32)
@@ -364,7 +353,7 @@ class _WideBlock(torch.autograd.Function):
                   tmap.data_ptr(), pack1.data_ptr(), goa.data_ptr(), ksel.data_ptr(), splits, Rpart.data_ptr())
         # (no weight needs a gradient: the weight-gradient pass and its fold are skipped, dL/dW2 below is unused)
         R = _colsum(Rpart) if need_w else torch.zeros(rows * H + H, dtype=torch.float64, device=dev)
-        sT = reduced(partT) if sync else None
+        sT = _reduced(partT, count) if sync else None
         g_ws = g_bs = None
         if fusedd:
             # BatchNorm-1 backward constants and dL/dW2 = R_S + D2 (W2 Gram) + E2 (x) suma: one launch

@@ -14,19 +14,19 @@ The pass over the B*N*K positions is one gather-extremum over every query's dist
 exists, forward or backward.  A block is
 
     forward   U = f^T Wf^T                                              the contraction kernel (apn_pw_contract)
-              ext, sel, ysum, BatchNorm's sums                          apn_la_pool_fwd (+ apn_la_stats_fold)
-              pack = BatchNorm's fold (running buffers updated)         apn_sa_bn_fold
+              ext, sel, ysum, BatchNorm's partial sums                  apn_la_pool_fwd
+              pack = BatchNorm's fold (running buffers updated)         batchnorm.pooled_stats_pack
               out = relu(scale ext + shift), channels first             apn_sa_wide_out
-    backward  g' = g [out > 0] scale, {sum g, sum g yhat}               apn_sa_wide_bwd_prep, apn_sa_wide_consts2
+    backward  g' = g [out > 0] scale, {sum g, sum g yhat}               apn_sa_wide_bwd_prep, batchnorm.dense_terms
               dU, dT (, dL/dp) per point through the inverse map        apn_la_pool_bwd   (no float atomics)
               dL/df = Wf^T dU, dL/dW = [dT^T p / r, dU^T f^T]           the contraction kernel
 
 Gradients are bit-identical from run to run.  With sync_bn the float64 sums are all-reduced over ranks where they
-leave the kernels (`fused_wide._bn_pack`'s exchange).
+leave the kernels (`fused_wide._reduced`'s exchange in the backward pass).
 """
 import torch
 
-from . import _lib, fused_wide, pointwise
+from . import _lib, batchnorm, fused_wide, pointwise
 from . import fused as _fz
 from .fused import _call
 
@@ -49,7 +49,7 @@ class _LocalAggregation(torch.autograd.Function):
         dev = f.device
         B, C, N = f.shape
         H = w.shape[0]
-        training = bn.training or not bn.track_running_stats
+        training = batchnorm.mode(bn)[0]
         sync = sync_bn and (_fz._world(True) > 1 or _fz.FORCE_PHASED)
         f32 = dict(dtype=torch.float32, device=dev)
         lib = _lib.load()
@@ -61,22 +61,12 @@ class _LocalAggregation(torch.autograd.Function):
             ext = torch.empty(B, N, H, **f32)
             sel = torch.empty(B, N, H, dtype=torch.uint8, device=dev)
             count = float(B * N * K_NS)
-            ysum = part = sums = None
-            if training:
-                rows = lib.apn_la_pool_rows(B, N)
-                ysum = torch.empty(B, N, H, **f32)
-                part = torch.empty(rows, 2 * H, dtype=torch.float64, device=dev)
+            rows = lib.apn_la_pool_rows(B, N) if training else 0
+            ysum = torch.empty(B, N, H, **f32) if training else None
+            part = torch.empty(rows, 2 * H, dtype=torch.float64, device=dev) if training else None
             _call("apn_la_pool_fwd", dev, B, N, H, K_NS, float(scale), U.data_ptr(), p.data_ptr(), W.data_ptr(), C + 3,
                   nbr.idx.data_ptr(), _fz._ptr(gamma), ext.data_ptr(), sel.data_ptr(), _fz._ptr(ysum), _fz._ptr(part))
-            if training:
-                sums = torch.empty(2 * H + 2, dtype=torch.float64, device=dev)
-                _call("apn_la_stats_fold", dev, part.data_ptr(), rows, H, count, sums.data_ptr())
-                if sync:
-                    _fz._allreduce_sum_(sums)
-            a = _fz._bn_args(bn)      # (gamma, beta, running_mean, running_var, nbt, eps, momentum, training)
-            pack = torch.empty(4 * H, **f32)
-            _call("apn_sa_bn_fold", dev, None, 0, _fz._ptr(sums), H, count, a[0], a[1], a[5], a[6], a[2], a[3], a[4],
-                  1 if training else 0, pack.data_ptr(), None, 0, None)
+            pack = batchnorm.pooled_stats_pack(part, rows, H, count, bn, training, sync)
             out = torch.empty(B, H, N, **f32)
             _call("apn_sa_wide_out", dev, B, N, H, ext.data_ptr(), pack.data_ptr(), C, None, None, None,
                   1 if relu else 0, out.data_ptr())
@@ -105,15 +95,8 @@ class _LocalAggregation(torch.autograd.Function):
         gs = g.stride()
         _call("apn_sa_wide_bwd_prep", dev, B, N, H, g.data_ptr(), gs[0], gs[1], gs[2], ext.data_ptr(), pack.data_ptr(),
               _fz._ptr(out_act), None, gsel.data_ptr(), partS.data_ptr())
-        sS = None
-        if sync:
-            sS = torch.cat([fused_wide._colsum(partS), torch.full((1,), count, dtype=torch.float64, device=dev),
-                            torch.ones(1, dtype=torch.float64, device=dev)])
-            _fz._allreduce_sum_(sS)
-        small = torch.empty(4 * H, **f32)
-        de, g_gamma, g_beta = small[:2 * H], small[2 * H:3 * H], small[3 * H:]
-        _call("apn_sa_wide_consts2", dev, None if sync else partS.data_ptr(), prow, _fz._ptr(sS), H, pack.data_ptr(), count,
-              1 if training else 0, de.data_ptr(), g_gamma.data_ptr(), g_beta.data_ptr())
+        de, g_gamma, g_beta = batchnorm.dense_terms(partS, prow, H, pack, count, training,
+                                                    fused_wide._reduced(partS, count) if sync else None)
         dU = torch.empty(B, N, H, **f32)
         dT = torch.empty(B, N, H, **f32)
         g_p = torch.empty(B, N, 3, **f32) if need_p else None

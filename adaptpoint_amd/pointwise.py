@@ -20,7 +20,8 @@ PointNeXt mirror), `matmul_nt` / `contract` (the contraction kernel on raw opera
 """
 import torch
 
-from . import _lib
+from . import _lib, batchnorm
+from .batchnorm import ptr
 from .fused import _call
 
 # bf16 planes per operand of the contractions: 3 = six MFMAs per product, fp32-class (~2e-7: what a stack of ~40
@@ -72,22 +73,12 @@ class _ConvBNAct(torch.autograd.Function):
         B, C, N = x.shape
         O = weight.shape[0]
         w = weight.detach().reshape(O, C).contiguous()
-        training = bn.training or not bn.track_running_stats
-        lib = _lib.load()
+        training = batchnorm.mode(bn)[0]
         y = torch.empty(B, O, N, device=dev)
-        tiles = lib.apn_pw_conv_tiles(B, N)
+        tiles = _lib.load().apn_pw_conv_tiles(B, N)
         part = torch.empty(tiles, 2, O, device=dev) if training else None
-        _call("apn_pw_conv_forward", dev, B, C, O, N, PRECISION, x.data_ptr(), w.data_ptr(), y.data_ptr(),
-              part.data_ptr() if training else None)
-        out = torch.empty_like(y)
-        stat = torch.empty(4, O, device=dev)
-        track = bn.track_running_stats and bn.running_mean is not None
-        _call("apn_pw_bn_act", dev, B, O, N, y.data_ptr(), part.data_ptr() if training else None, tiles,
-              gamma.data_ptr() if gamma is not None else None, beta.data_ptr() if beta is not None else None,
-              float(bn.eps), float(bn.momentum if bn.momentum is not None else 0.0), int(training), int(relu),
-              bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-              bn.num_batches_tracked.data_ptr() if (track and training and bn.num_batches_tracked is not None) else None,
-              stat.data_ptr(), out.data_ptr())
+        _call("apn_pw_conv_forward", dev, B, C, O, N, PRECISION, x.data_ptr(), w.data_ptr(), y.data_ptr(), ptr(part))
+        out, stat = batchnorm.bn_act(y, part, tiles, gamma, beta, bn, relu)
         ctx.save_for_backward(x, w, y, stat)
         ctx.cfg = (training, relu, gamma is not None, beta is not None, weight.shape)
         return out
@@ -100,13 +91,8 @@ class _ConvBNAct(torch.autograd.Function):
         B, C, N = x.shape
         O = w.shape[0]
         lib = _lib.load()
-        g = g.contiguous()
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        part_b = torch.empty(lib.apn_pw_bn_act_grad_splits(B, O), 2, O, device=dev)
-        gy = torch.empty_like(y)
-        ggb = torch.empty(2, O, device=dev)
-        _call("apn_pw_bn_act_grad", dev, B, O, N, g.data_ptr(), y.data_ptr(), stat.data_ptr(), int(training), int(relu),
-              part_b.data_ptr(), gy.data_ptr(), ggb[0].data_ptr(), ggb[1].data_ptr())
+        gy, g_gamma, g_beta = batchnorm.bn_act_grad(g, y, stat, training, relu, has_gamma, has_beta)
         gx = gw = None
         if need_x:
             gx = torch.empty_like(x)
@@ -118,7 +104,7 @@ class _ConvBNAct(torch.autograd.Function):
             _call("apn_pw_conv_grad_weight", dev, B, C, O, N, PRECISION, gy.data_ptr(), x.data_ptr(), scratch.data_ptr(),
                   gw.data_ptr())
             gw = gw.view(wshape)
-        return gx, gw, (ggb[0] if has_gamma else None), (ggb[1] if has_beta else None), None, None
+        return gx, gw, g_gamma, g_beta, None, None
 
 
 class _NoNorm:
@@ -128,7 +114,7 @@ class _NoNorm:
     track_running_stats = True
     momentum = 0.0
     eps = 0.0
-    num_batches_tracked = None
+    weight = bias = num_batches_tracked = None
     _cache = {}
 
     def __init__(self, channels, device):
@@ -163,7 +149,7 @@ class _ConvMax(torch.autograd.Function):
         out = torch.empty(B, O, device=dev)
         idx = torch.empty(B, O, dtype=torch.int32, device=dev)
         _call("apn_pw_conv_max_forward", dev, B, C, O, N, PRECISION, x.data_ptr(), w.data_ptr(),
-              bias.data_ptr() if bias is not None else None, int(relu), tile_val.data_ptr(), tile_idx.data_ptr(),
+              ptr(bias), int(relu), tile_val.data_ptr(), tile_idx.data_ptr(),
               out.data_ptr(), idx.data_ptr())
         ctx.save_for_backward(x, w, out, idx)
         ctx.cfg = (relu, bias is not None, weight.shape)
@@ -183,8 +169,7 @@ class _ConvMax(torch.autograd.Function):
         gw = torch.empty(O, C, device=dev)
         gb = torch.empty(O, device=dev) if has_bias else None
         _call("apn_pw_conv_max_backward", dev, B, C, O, N, g.data_ptr(), out.data_ptr(), idx.data_ptr(), x.data_ptr(),
-              w.data_ptr(), int(relu), xsel.data_ptr(), gx.data_ptr() if gx is not None else None, gw.data_ptr(),
-              gb.data_ptr() if gb is not None else None)
+              w.data_ptr(), int(relu), xsel.data_ptr(), ptr(gx), gw.data_ptr(), ptr(gb))
         return gx, gw.view(wshape), gb, None
 
 
@@ -282,8 +267,7 @@ def contract(nbatch, R, Q, K, a, a_batch, lda, a_kcont, b, b_batch, ldb, b_kcont
         splits = lib.apn_pw_contract_splits(nbatch, R, Q, K)
         scratch = torch.empty(splits, R, Q, device=out.device)
     _call("apn_pw_contract", out.device, nbatch, R, Q, K, a.data_ptr(), a_batch, lda, int(a_kcont), b.data_ptr(), b_batch,
-          ldb, int(b_kcont), out.data_ptr(), d_batch, Q if ldd is None else ldd, splits,
-          scratch.data_ptr() if scratch is not None else None, PRECISION)
+          ldb, int(b_kcont), out.data_ptr(), d_batch, Q if ldd is None else ldd, splits, ptr(scratch), PRECISION)
     return out
 
 

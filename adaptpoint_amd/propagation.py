@@ -16,8 +16,8 @@ neither the interpolated (B,C2,n) tensor nor the (B,C1+C2,n) concatenation exist
     forward   a = W[:, :C1] f1 | u = W[:, C1:] f2      ONE launch of the contraction kernel (apn_pw_contract2), the
                                                         weight's column blocks addressed in place
               y = a + blend(u) (+ BatchNorm partials)   apn_fp_blend_stats
-              out = relu(bn(y))                         apn_pw_bn_act (training); in eval mode the previous launch does it
-    backward  gy = dL/dy                                apn_pw_bn_act_grad
+              out = relu(bn(y))                         batchnorm.bn_act (training); in eval mode the previous launch does it
+    backward  gy = dL/dy                                batchnorm.bn_act_grad
               gu = blend^T(gy)                          apn_three_interpolate_grad on O channels into a zeroed (B,O,m)
               g_f1 = W[:, :C1]^T gy | g_f2 = W[:, C1:]^T gu            one two-problem launch
               gW[:, :C1] = sum gy f1^T | gW[:, C1:] = sum gu f2^T      one two-problem launch + one fold
@@ -36,7 +36,8 @@ import ctypes
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, batchnorm
+from .batchnorm import ptr
 
 
 def supported(f1, f2, conv, bn):
@@ -69,19 +70,6 @@ def blend(u, nearest, weights):
     return out
 
 
-def _batch_norm(y, bn):
-    """`bn(y)` for a BatchNorm module through F.batch_norm (buffers updated as the module's forward updates them)."""
-    factor = 0.0 if bn.momentum is None else bn.momentum
-    if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-        if bn.momentum is None:
-            factor = 1.0 / float(bn.num_batches_tracked)
-    use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
-    keep = not bn.training or bn.track_running_stats
-    return F.batch_norm(y, bn.running_mean if keep else None, bn.running_var if keep else None, bn.weight, bn.bias,
-                        use_batch, factor, bn.eps)
-
-
 def _propagate_torch(f1, f2, nearest, weights, conv, bn, relu):
     c1 = 0 if f1 is None else f1.shape[1]
     w = conv.weight.reshape(conv.out_channels, conv.in_channels, 1)
@@ -90,7 +78,7 @@ def _propagate_torch(f1, f2, nearest, weights, conv, bn, relu):
         y = F.conv1d(f1, w[:, :c1]) + y
     if conv.bias is not None:
         y = y + conv.bias.view(1, -1, 1)
-    y = _batch_norm(y, bn)
+    y = batchnorm.module_forward(y, bn)
     return torch.relu(y) if relu else y
 
 
@@ -125,8 +113,7 @@ class _HoistedPropagation(torch.autograd.Function):
         C = C1 + C2
         O = weight.shape[0]
         w = weight.detach().reshape(O, C).contiguous()
-        training = bn.training or not bn.track_running_stats
-        lib = _lib.load()
+        training = batchnorm.mode(bn)[0]
         u = torch.empty(B, O, m, device=dev)
         a = None
         if f1 is not None:
@@ -137,25 +124,19 @@ class _HoistedPropagation(torch.autograd.Function):
         else:
             contract(B, O, m, C2, w, 0, C, True, f2, C2 * m, m, False, u, d_batch=O * m, ldd=m)
         needs_grad = any(ctx.needs_input_grad[:5])
-        gp = lambda t: t.data_ptr() if t is not None else None
-        track = bn.track_running_stats and bn.running_mean is not None
-        out = torch.empty(B, O, n, device=dev)
-        stat = torch.empty(4, O, device=dev)
         if training:
             y = a if a is not None else torch.empty(B, O, n, device=dev)       # (the blend adds into the skip product)
-            tiles = lib.apn_pw_conv_tiles(B, n)
+            tiles = _lib.load().apn_pw_conv_tiles(B, n)
             part = torch.empty(tiles, 2, O, device=dev)
-            _call("apn_fp_blend_stats", dev, B, O, m, n, gp(a), u.data_ptr(), nearest.data_ptr(), weights.data_ptr(),
+            _call("apn_fp_blend_stats", dev, B, O, m, n, ptr(a), u.data_ptr(), nearest.data_ptr(), weights.data_ptr(),
                   y.data_ptr(), part.data_ptr(), 1, None, None, None, None, float(bn.eps), int(relu), None, None)
-            _call("apn_pw_bn_act", dev, B, O, n, y.data_ptr(), part.data_ptr(), tiles, gp(gamma), gp(beta), float(bn.eps),
-                  float(bn.momentum if bn.momentum is not None else 0.0), 1, int(relu),
-                  bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                  bn.num_batches_tracked.data_ptr() if (track and bn.num_batches_tracked is not None) else None,
-                  stat.data_ptr(), out.data_ptr())
+            out, stat = batchnorm.bn_act(y, part, tiles, gamma, beta, bn, relu)
         else:
             y = (a if a is not None else torch.empty(B, O, n, device=dev)) if needs_grad else None
-            _call("apn_fp_blend_stats", dev, B, O, m, n, gp(a), u.data_ptr(), nearest.data_ptr(), weights.data_ptr(),
-                  gp(y), None, 0, gp(gamma), gp(beta), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+            out = torch.empty(B, O, n, device=dev)
+            stat = torch.empty(4, O, device=dev)
+            _call("apn_fp_blend_stats", dev, B, O, m, n, ptr(a), u.data_ptr(), nearest.data_ptr(), weights.data_ptr(),
+                  ptr(y), None, 0, ptr(gamma), ptr(beta), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                   float(bn.eps), int(relu), stat.data_ptr(), out.data_ptr())
         ctx.save_for_backward(f1, f2, w, y, stat, nearest, weights)
         ctx.cfg = (training, relu, gamma is not None, beta is not None, weight.shape)
@@ -175,14 +156,9 @@ class _HoistedPropagation(torch.autograd.Function):
         C = C1 + C2
         O = w.shape[0]
         lib = _lib.load()
-        g = g.contiguous()
         need_f1 = f1 is not None and ctx.needs_input_grad[0]
         need_f2, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        part_b = torch.empty(lib.apn_pw_bn_act_grad_splits(B, O), 2, O, device=dev)
-        gy = torch.empty(B, O, n, device=dev)
-        ggb = torch.empty(2, O, device=dev)
-        _call("apn_pw_bn_act_grad", dev, B, O, n, g.data_ptr(), y.data_ptr(), stat.data_ptr(), int(training), int(relu),
-              part_b.data_ptr(), gy.data_ptr(), ggb[0].data_ptr(), ggb[1].data_ptr())
+        gy, g_gamma, g_beta = batchnorm.bn_act_grad(g, y, stat, training, relu, has_gamma, has_beta)
         g_f1 = g_f2 = gw = None
         if need_f2 or need_w:
             gu = zeros(B, O, m, device=dev)                  # a kernel fill: capturable (no memset node)
@@ -215,7 +191,7 @@ class _HoistedPropagation(torch.autograd.Function):
             else:
                 contract(B, O, C2, m, gu, O * m, m, True, f2, C2 * m, m, True, gw, reduce=True)
             gw = gw.view(wshape)
-        return (g_f1, g_f2, gw, (ggb[0] if has_gamma else None), (ggb[1] if has_beta else None), None, None, None, None)
+        return g_f1, g_f2, gw, g_gamma, g_beta, None, None, None, None
 
 
 def block_parts(block):

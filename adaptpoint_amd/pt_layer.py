@@ -20,7 +20,7 @@ sum has a fixed order: two runs give the same bits.
 """
 import torch
 
-from . import _lib
+from . import _lib, batchnorm
 from .fused import _call, _ptr
 
 
@@ -38,7 +38,7 @@ def _bn_forward(bn, sums, count):
     if sums is not None:
         mean = sums[:C] / count
         var = (sums[C:] / count - mean * mean).clamp_min(0.0)
-        if bn.track_running_stats and bn.training:
+        if batchnorm.mode(bn)[1] and bn.training:
             m = bn.momentum
             bn.running_mean.mul_(1.0 - m).add_((m * mean).to(bn.running_mean.dtype))
             bn.running_var.mul_(1.0 - m).add_((m * var * (count / max(count - 1.0, 1.0))).to(bn.running_var.dtype))
@@ -90,7 +90,7 @@ class _PtAttention(torch.autograd.Function):
         idx = graph.idx
         f32 = dict(dtype=torch.float32, device=dev)
         lib = _lib.load()
-        training = bn1.training or not bn1.track_running_stats
+        training = batchnorm.mode(bn1)[0]
         with torch.no_grad():
             qkv, h = qkv.contiguous(), h.contiguous()
             wts = torch.cat([W2.reshape(-1), b2, W3.t().reshape(-1), b3, W4.reshape(-1), b4]).float().contiguous()

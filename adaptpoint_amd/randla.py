@@ -36,6 +36,8 @@ reference takes the value from `torch_points_kernels.knn`; which of the two that
 import torch
 import torch.nn as nn
 
+from . import batchnorm
+
 RL_WIDTHS = (8, 16, 32, 64, 128)
 RL_K_MAX = 32
 _MAX_POINTS = 2 ** 24
@@ -168,18 +170,16 @@ class _EncodePool(torch.autograd.Function):
         dev = coords.device
         B, N, K = idx.shape
         C = w.shape[0]
-        training = bn.training or not bn.track_running_stats
-        track = bn.track_running_stats and bn.running_mean is not None
+        bna = batchnorm.args(bn)
+        training = bool(bna.training)
         f32 = dict(dtype=torch.float32, device=dev)
         with torch.no_grad():
             w2 = w.detach().reshape(C, 10).contiguous()
             wf = torch.empty(11 * C + 10, **f32)
             stat = torch.empty(3 * C, dtype=torch.float64, device=dev)
             _call("apn_rl_fold", dev, C, _ptr(mom) if training else None, float(B * N * K), w2.data_ptr(), _ptr(b),
-                  _ptr(gamma), _ptr(beta), float(bn.eps), float(bn.momentum), int(training),
-                  bn.running_mean.data_ptr() if track else None, bn.running_var.data_ptr() if track else None,
-                  bn.num_batches_tracked.data_ptr() if (track and training and bn.num_batches_tracked is not None)
-                  else None, wf.data_ptr(), stat.data_ptr())
+                  _ptr(gamma), _ptr(beta), bna.eps, bna.momentum, bna.training, bna.running_mean, bna.running_var,
+                  bna.num_batches_tracked, wf.data_ptr(), stat.data_ptr())
             a = A.detach()[:C, :C].contiguous()
             at = A.detach()[:C, :C].t().contiguous()
             pooled = torch.empty(B, C, N, **f32)
@@ -283,7 +283,7 @@ class LocalFeatureAggregation(nn.Module):
             root = self.dist == 'euclidean'
             bns = (self.lse1.mlp.batch_norm, self.lse2.mlp.batch_norm)
             mom = (encoding_moments(coords, idx, dist2, root)
-                   if any(bn.training or not bn.track_running_stats for bn in bns) else None)
+                   if any(batchnorm.mode(bn)[0] for bn in bns) else None)
             x = _per_point(self.pool1.mlp, encode_pool(self.lse1, self.pool1, coords, x, idx, dist2, mom, root), True)
             x = _per_point(self.pool2.mlp, encode_pool(self.lse2, self.pool2, coords, x, idx, dist2, mom, root), True)
         else:
