@@ -142,6 +142,9 @@ SIGNATURES = {
     "apn_pw_contract2_splits": [_c_int] * 9,
     "apn_pw_contract2": [_c_int] * 3 + [_c_void_p] * 16,
     "apn_fp_blend_stats": [_c_int] * 4 + [_c_void_p] * 6 + [_c_int] + [_c_void_p] * 4 + [_c_float, _c_int] + [_c_void_p] * 3,
+    "apn_fp_blend_stats_cond": [_c_int] * 4 + [_c_void_p] * 7 + [_c_int] + [_c_void_p] * 4 + [_c_float, _c_int]
+                               + [_c_void_p] * 3,
+    "apn_fp_cond_grad": [_c_int] * 3 + [_c_void_p] * 3,
     "apn_pw_transpose": [_c_int] * 3 + [_c_void_p] * 3,
     "apn_three_nn_weights": [_c_longlong] + [_c_void_p] * 3,
     "apn_anchor_transforms": [_c_int] + [_c_void_p] * 3 + [_c_float] * 3 + [_c_void_p] * 3,
@@ -163,6 +166,7 @@ SIGNATURES = {
     "apn_rsmix_mix": [_c_int] * 4 + [_c_void_p] * 8,
     "apn_cloud_transform": [_c_int] * 4 + [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 8,
     "apn_cls_confusion": [_c_int] * 2 + [_c_void_p, _c_int] + [_c_void_p] * 5,
+    "apn_part_ious": [_c_int] * 5 + [_c_void_p] * 13,
     "apn_la_pool_rows": [_c_int] * 2,
     "apn_la_pool_fwd": [_c_int] * 4 + [_c_float] + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 7,
     "apn_la_stats_fold": [_c_void_p, _c_int, _c_int, _c_double, _c_void_p, _c_void_p],

@@ -122,6 +122,14 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
 }
 
 
+// true when (v, i) comes before (best, bi) in torch.argmax's order: a NaN beats every number (the lower index among
+// NaNs), then the larger value, then the lower index (csrc/cls_metrics.hip, csrc/part_metrics.hip)
+__device__ __forceinline__ bool argmax_better(float v, int i, float best, int bi) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > best || (v == best && i < bi);
+}
+
 // Raising a kernel's dynamic-LDS limit is a property of the CURRENT DEVICE's copy of the function: the "done" flag is
 // kept per device (bit d of the mask), so a process that launches on a second GPU sets the attribute there too; the
 // atomic mask makes the first launches of two host threads safe (setting the attribute twice is harmless).

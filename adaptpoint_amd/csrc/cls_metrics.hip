@@ -21,13 +21,6 @@ namespace apn {
 constexpr int CM_THREADS = 256;
 constexpr int CM_ROWS = CM_THREADS / APN_WAVE;
 
-// true when (v, i) comes before (best, bi) in torch.argmax's order
-__device__ __forceinline__ bool argmax_better(float v, int i, float best, int bi) {
-    const bool vn = v != v, bn = best != best;
-    if (vn || bn) return vn && (!bn || i < bi);
-    return v > best || (v == best && i < bi);
-}
-
 __global__ __launch_bounds__(CM_THREADS) void cls_confusion_kernel(int b, int k, const float *__restrict__ logits,
                                                                    int ld, const int *__restrict__ target,
                                                                    const int *__restrict__ valid,

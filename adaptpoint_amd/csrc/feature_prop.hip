@@ -14,6 +14,12 @@
 // formed exactly as pw_gemm_kernel's epilogue forms them (per 32 columns around a shift, the four blocks combined in
 // float64: see the comment there) -- in eval mode scale, shift and ReLU are applied here and nothing follows.
 // Every sum runs in a fixed order: no float atomic, bit-identical results from run to run.
+//
+// The conditioned form (apn_fp_blend_stats_cond) serves a block whose concatenation starts with a per-cloud vector
+// repeated over the points, W [cond 1^T ; f1 ; blend(f2)]: the vector's share of the product is one number per (cloud,
+// channel), cvec[b][o] = (W[:, :Cc] cond_b)[o], and the launch adds it LAST -- y = (a + blend(u)) + cvec -- before the
+// statistics.  It is the same kernel with one more pointer (null: the unconditioned block, the same bits as before).
+// Its gradient is the row sum gc[b][o] = sum_i gy[b][o][i] (fp_cond_grad_kernel, one wave per row, fixed order).
 #include <hip/hip_runtime.h>
 
 #include "apn_common.h"
@@ -33,7 +39,7 @@ __global__ __launch_bounds__(FP_THREADS) void fp_blend_stats_kernel(
     int O, int m, int n, const float *a, const float *__restrict__ u, const int *__restrict__ idx,
     const float *__restrict__ weight, float *y, float *__restrict__ part, int training, const float *__restrict__ gamma,
     const float *__restrict__ beta, const float *__restrict__ run_mean, const float *__restrict__ run_var, float eps,
-    int relu, float *__restrict__ stat, float *__restrict__ out) {
+    int relu, float *__restrict__ stat, float *__restrict__ out, const float *__restrict__ cvec) {
     __shared__ __attribute__((aligned(16))) float tile[FP_OC * FP_ROW];
     const int t = threadIdx.x, col = t & (FP_T - 1), half = t >> 7;
     const int n0 = blockIdx.x * FP_T, o0 = blockIdx.y * FP_OC, b = blockIdx.z;
@@ -50,8 +56,9 @@ __global__ __launch_bounds__(FP_THREADS) void fp_blend_stats_kernel(
     const float *ab = a ? a + ((size_t)b * O + o0) * n + ic : nullptr;
     float *yb = y ? y + ((size_t)b * O + o0) * n + i : nullptr;
     float *ob = out ? out + ((size_t)b * O + o0) * n + i : nullptr;
+    const float *cb = cvec ? cvec + (size_t)b * O + o0 : nullptr;     // the cloud's conditioning bias (workgroup-uniform)
     for (int k0 = half; k0 < nc; k0 += 2 * FP_U) {
-        float va[FP_U], v0[FP_U], v1[FP_U], v2[FP_U];
+        float va[FP_U], v0[FP_U], v1[FP_U], v2[FP_U], vc[FP_U];
 #pragma unroll
         for (int e = 0; e < FP_U; ++e) {
             const int o = k0 + 2 * e;
@@ -59,6 +66,7 @@ __global__ __launch_bounds__(FP_THREADS) void fp_blend_stats_kernel(
             const float *ur = ub + (size_t)oc * m;
             v0[e] = ur[i0]; v1[e] = ur[i1]; v2[e] = ur[i2];
             va[e] = ab ? ab[(size_t)oc * n] : 0.0f;
+            vc[e] = cb ? cb[oc] : 0.0f;
         }
 #pragma unroll
         for (int e = 0; e < FP_U; ++e) {
@@ -67,6 +75,7 @@ __global__ __launch_bounds__(FP_THREADS) void fp_blend_stats_kernel(
                 // the interpolation's own order (three_interpolate_kernel), then the skip product
                 float v = __builtin_fmaf(w2, v2[e], __builtin_fmaf(w1, v1[e], w0 * v0[e]));
                 v = va[e] + v;
+                if (cb) v = v + vc[e];                      // (a + blend(u)) + cvec: the conditioning bias last
                 if (training) {
                     tile[o * FP_ROW + col] = v;
                     if (in) yb[(size_t)o * n] = v;
@@ -137,13 +146,29 @@ __global__ __launch_bounds__(FP_THREADS) void fp_blend_stats_kernel(
     }
 }
 
-}  // namespace apn
+constexpr int FP_GC_THREADS = 256;
+constexpr int FP_GC_ROWS = FP_GC_THREADS / APN_WAVE;
 
-extern "C" int apn_fp_blend_stats(int b, int o, int m, int n, const float *a, const float *u, const int *idx,
-                                  const float *weight, float *y, float *part, int training, const float *gamma,
-                                  const float *beta, const float *run_mean, const float *run_var, float eps, int relu,
-                                  float *stat, float *out, void *stream) {
-    using namespace apn;
+// gc[row] = sum_i gy[row][i] for the rows = B * O rows of n floats: one wave per row.  Lane l adds its elements
+// l, l + 64, ... in ascending order; the 64 lane sums then meet in a fixed xor butterfly (every lane ends with the same
+// total: float addition commutes, and the pairing is fixed).  One owner per output, no atomic: the same bits on every run.
+__global__ __launch_bounds__(FP_GC_THREADS) void fp_cond_grad_kernel(long long rows, int n, const float *__restrict__ gy,
+                                                                     float *__restrict__ gc) {
+    const int lane = threadIdx.x % APN_WAVE;
+    const long long row = (long long)blockIdx.x * FP_GC_ROWS + threadIdx.x / APN_WAVE;
+    if (row >= rows) return;                           // wave-uniform
+    const float *src = gy + (size_t)row * n;
+    float s = 0.0f;
+    for (int i = lane; i < n; i += APN_WAVE) s += src[i];
+#pragma unroll
+    for (int k = APN_WAVE / 2; k > 0; k >>= 1) s += __shfl_xor(s, k, APN_WAVE);
+    if (lane == 0) gc[row] = s;
+}
+
+static int fp_blend_launch(int b, int o, int m, int n, const float *a, const float *u, const int *idx, const float *weight,
+                           float *y, float *part, int training, const float *gamma, const float *beta,
+                           const float *run_mean, const float *run_var, float eps, int relu, float *stat, float *out,
+                           const float *cvec, void *stream) {
     if (b < 0 || o < 0 || m < 0 || n < 0 || b > 65535) return APN_EINVAL;
     if (b == 0 || o == 0 || n == 0) return APN_OK;
     if (m == 0 || !u || !idx || !weight) return APN_EINVAL;
@@ -151,7 +176,42 @@ extern "C" int apn_fp_blend_stats(int b, int o, int m, int n, const float *a, co
     const dim3 grid((n + FP_T - 1) / FP_T, (o + FP_OC - 1) / FP_OC, b);
     if (grid.y > 65535) return APN_EINVAL;
     hipLaunchKernelGGL(fp_blend_stats_kernel, grid, dim3(FP_THREADS), 0, (hipStream_t)stream, o, m, n, a, u, idx, weight,
-                       y, part, training, gamma, beta, run_mean, run_var, eps, relu, stat, out);
+                       y, part, training, gamma, beta, run_mean, run_var, eps, relu, stat, out, cvec);
+    APN_LAUNCH_CHECK();
+    return APN_OK;
+}
+
+}  // namespace apn
+
+extern "C" int apn_fp_blend_stats(int b, int o, int m, int n, const float *a, const float *u, const int *idx,
+                                  const float *weight, float *y, float *part, int training, const float *gamma,
+                                  const float *beta, const float *run_mean, const float *run_var, float eps, int relu,
+                                  float *stat, float *out, void *stream) {
+    return apn::fp_blend_launch(b, o, m, n, a, u, idx, weight, y, part, training, gamma, beta, run_mean, run_var, eps, relu,
+                                stat, out, nullptr, stream);
+}
+
+extern "C" int apn_fp_blend_stats_cond(int b, int o, int m, int n, const float *a, const float *u, const int *idx,
+                                       const float *weight, const float *c, float *y, float *part, int training,
+                                       const float *gamma, const float *beta, const float *run_mean,
+                                       const float *run_var, float eps, int relu, float *stat, float *out, void *stream) {
+    if (b < 0 || o < 0 || m < 0 || n < 0 || b > 65535) return APN_EINVAL;
+    if (b == 0 || o == 0 || n == 0) return APN_OK;
+    if (!c) return APN_EINVAL;
+    return apn::fp_blend_launch(b, o, m, n, a, u, idx, weight, y, part, training, gamma, beta, run_mean, run_var, eps, relu,
+                                stat, out, c, stream);
+}
+
+extern "C" int apn_fp_cond_grad(int b, int o, int n, const float *gy, float *gc, void *stream) {
+    using namespace apn;
+    if (b < 0 || o < 0 || n < 0 || b > 65535) return APN_EINVAL;
+    if (b == 0 || o == 0) return APN_OK;
+    if (!gc || (n > 0 && !gy)) return APN_EINVAL;
+    const long long rows = (long long)b * o;
+    const long long blocks = (rows + FP_GC_ROWS - 1) / FP_GC_ROWS;
+    if (blocks > 2147483647LL) return APN_EINVAL;
+    hipLaunchKernelGGL(fp_cond_grad_kernel, dim3((unsigned)blocks), dim3(FP_GC_THREADS), 0, (hipStream_t)stream, rows, n, gy,
+                       gc);
     APN_LAUNCH_CHECK();
     return APN_OK;
 }

@@ -344,10 +344,11 @@ class FeaturePropagation(nn.Module):
     blocks.  `upsample=False` is the global variant (mean-pooled feature broadcast back).  Sub-module
     names (`convs.<i>.0/1`, `linear1`, `linear2`) are the reference's."""
 
-    def __init__(self, mlp, upsample=True, norm_args=None, act_args=None, hoisted=False):
+    def __init__(self, mlp, upsample=True, norm_args=None, act_args=None, hoisted=False, fused=False):
         super().__init__()
         from .set_abstraction import convblock
         self.hoisted = hoisted     # the first block of `convs` in adaptpoint_amd.propagation's form (upsample=True only)
+        self.fused = fused         # hoisted: the later blocks of `convs` on the per-point layer kernels (fixed-order sums)
         norm_args = {'norm': 'bn1d'} if norm_args is None else norm_args
         act_args = {'act': 'relu'} if act_args is None else act_args
         mlp = list(mlp)
@@ -361,8 +362,10 @@ class FeaturePropagation(nn.Module):
             self.convs = nn.Sequential(*[convblock(mlp[i], mlp[i + 1], 1, norm_args=norm_args, act_args=act_args)
                                          for i in range(len(mlp) - 1)])
 
-    def forward(self, pf1, pf2=None):
-        from . import propagation
+    def forward(self, pf1, pf2=None, cond=None):
+        """cond (B,Cc) or None: a per-cloud vector repeated over the dense points in FRONT of f1 (the class
+        conditioning of `partseg.PointNextPartDecoder`); hoisted, it never becomes a (B,Cc,n) tensor."""
+        from . import pointwise, propagation
         from .layers import three_interpolation, three_nn_weights
         if pf2 is None:
             _, f = pf1
@@ -372,10 +375,14 @@ class FeaturePropagation(nn.Module):
         parts = propagation.block_parts(self.convs[0]) if self.hoisted else None
         if parts is not None:
             nearest, weights = three_nn_weights(p1.contiguous(), p2.contiguous())
-            f = propagation.propagate(None if f1 is None else f1.contiguous(), f2.contiguous(), nearest, weights, *parts)
+            f = propagation.propagate(None if f1 is None else f1.contiguous(), f2.contiguous(), nearest, weights, *parts,
+                                      cond=None if cond is None else cond.contiguous())
             for block in list(self.convs)[1:]:
-                f = block(f)
+                f = pointwise.run_block(f, block, True) if self.fused else block(f)
             return f
+        if cond is not None:
+            rep = cond.unsqueeze(-1).expand(-1, -1, p1.shape[1])
+            f1 = rep if f1 is None else torch.cat((rep, f1), dim=1)
         up = three_interpolation(p1, p2, f2)
         return self.convs(up if f1 is None else torch.cat((f1, up), dim=1))
 

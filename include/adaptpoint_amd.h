@@ -692,6 +692,19 @@ APN_API int apn_fp_blend_stats(int b, int o, int m, int n, const float *a, const
                                const float *beta, const float *run_mean, const float *run_var, float eps, int relu,
                                float *stat, float *out, void *stream);
 
+/* The same block with a per-cloud conditioning vector in front of the concatenation, W [cond 1^T ; f1 ; blend(f2)]
+ * (PointNextPartDecoder's class conditioning, openpoints/models/backbone/pointnext.py:626-663): the vector's share of the
+ * product is c (B,O), c[b] = W[:, :Cc] cond_b, one number per (cloud, channel), and
+ *     y[b][o][i] = (a[b][o][i] + blend(u)[b][o][i]) + c[b][o]         -- this association order; a null: blend(u) + c
+ * through the SAME kernel as apn_fp_blend_stats (one more pointer); every other argument as there.  c null -> APN_EINVAL.
+ * _cond_grad: gc (B,O) = sum_i gy[b][o][i], the gradient with respect to c: one wave per row, lane l adds elements
+ *   l, l + 64, ... in ascending order, then a fixed butterfly over the lanes; no atomic, bit-identical from run to run. */
+APN_API int apn_fp_blend_stats_cond(int b, int o, int m, int n, const float *a, const float *u, const int *idx,
+                                    const float *weight, const float *c, float *y, float *part, int training,
+                                    const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                    float eps, int relu, float *stat, float *out, void *stream);
+APN_API int apn_fp_cond_grad(int b, int o, int n, const float *gy, float *gc, void *stream);
+
 /* out[z][j][i] = in[z][i][j] for in (nbatch, r, c) float32, contiguous: the layout change between the per-point layers'
  * (B, C, N) and the grouper's / attention's (B, N, C) (generator_component4_15.py:650-657 permutes and lets PyTorch copy). */
 APN_API int apn_pw_transpose(int nbatch, int r, int c, const float *in, float *out, void *stream);
@@ -778,6 +791,23 @@ APN_API int apn_cloud_transform(int b, int n, int n_raw, int s, const float *raw
  * Integer atomics: exact and the same on every run. */
 APN_API int apn_cls_confusion(int b, int k, const float *logits, int ld, const int *target, const int *valid,
                               unsigned long long *cm, int *pred, void *stream);
+
+/* The part-segmentation metric of an evaluation batch (examples/shapenetpart/train_adapt.py: get_ins_mious :77-107 fed
+ * `logits.max(dim=1)[1]`, and validate's accumulation :576-582), two launches, no host read (csrc/part_metrics.hip):
+ *   logits (b, c, n) float32, c <= 64 part labels; target (b, n) int32; cls (b,) int32 in [0, s);
+ *   part_offset (s + 1) / part_ids (nparts) int32: category k's parts are part_ids[part_offset[k] .. part_offset[k+1]),
+ *   in the order the mean runs over them; valid (b,) int32 or NULL: shapes with valid[i] == 0 are padding.
+ *   Prediction: the first channel of the maximum; a NaN beats every number and the first NaN wins (torch's max).
+ *   ious (b,) float32, written: the shape's mean over its category's parts of float32(100 I) / float32(U), 100 where
+ *   U == 0; a predicted or target label outside the category's list is in no part; -1 for padding; -2 for a REJECTED
+ *   shape (class outside [0, s), CSR range empty, longer than 64 or outside [0, nparts], part id outside [0, c)).
+ *   cls_sum (s) float32, cls_num (s) int32, ins_sum (1) float64, ins_num (1) int32, rejected (1) int32 (may be NULL):
+ *   added to in ascending shape order and never cleared, so the totals do not depend on the split into batches.
+ * Integer LDS atomics and fixed-order sums only: the same bits on every run.
+ * c outside [1, 64], s < 1, nparts < 1, a negative size or a missing pointer -> APN_EINVAL; b == 0 -> APN_OK. */
+APN_API int apn_part_ious(int b, int c, int n, int s, int nparts, const float *logits, const int *target, const int *cls,
+                          const int *part_offset, const int *part_ids, const int *valid, float *ious, float *cls_sum,
+                          int *cls_num, double *ins_sum, int *ins_num, int *rejected, void *stream);
 
 /* The last layer of the discriminator's group-all stage with its pooling
  * (openpoints/models_adaptpoint/point_discriminator.py:183-189: conv -> ReLU -> max over the cloud's points), fused:
