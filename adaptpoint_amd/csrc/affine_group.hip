@@ -17,8 +17,9 @@
 // LDS, written by channel lanes, read back along positions, so both the gather and the store are contiguous.  The
 // gradient arrives as rows (B, S K, O) (one tiled transpose of dL/dy, apn_pw_transpose) for the same reason.
 //
-// Every sum runs in an order fixed by the shapes: no float atomic, two runs give the same bits.  Every index read from
-// idx / fps_idx is clamped into its cloud.
+// Every sum runs in an order fixed by the shapes: no float atomic, two runs give the same bits.  The fold of the float64
+// partial rows (apn_ag_fold) is csrc/col_sums.hip's, at 4 lanes.  Every index read from idx / fps_idx is clamped into its
+// cloud.
 #include <hip/hip_runtime.h>
 
 #include "apn_common.h"
@@ -77,21 +78,6 @@ __global__ __launch_bounds__(AG_THREADS) void ag_moments_kernel(int N, int S, in
         const double *r = red[threadIdx.x];
         part[((size_t)blockIdx.x * gridDim.y + b) * 2 + threadIdx.x] = ((r[0] + r[1]) + r[2]) + r[3];
     }
-}
-
-// out[col] = sum over rows ascending inside each of four row ranges, the four ranges then added in order.
-// grid (ceil(ncol / 64)); thread (col = t & 63, range = t >> 6)
-__global__ __launch_bounds__(AG_THREADS) void ag_fold_kernel(int rows, int ncol, const double *__restrict__ part,
-                                                             double *__restrict__ out) {
-    __shared__ double red[4][64];
-    const int cl = threadIdx.x & 63, seg = threadIdx.x >> 6, col = blockIdx.x * 64 + cl;
-    const int per = (rows + 3) / 4, r0 = seg * per, r1 = min(rows, r0 + per);
-    double a = 0.0;
-    if (col < ncol)
-        for (int r = r0; r < r1; ++r) a += part[(size_t)r * ncol + col];
-    red[seg][cl] = a;
-    __syncthreads();
-    if (seg == 0 && col < ncol) out[col] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
 }
 
 // ---------------------------------------------------------------------------------------------- combine, forward
@@ -391,10 +377,7 @@ extern "C" int apn_ag_fold(int rows, int ncol, const double *part, double *out, 
     if (rows < 0 || ncol < 0) return APN_EINVAL;
     if (ncol == 0) return APN_OK;
     if (!out || (rows > 0 && !part)) return APN_EINVAL;
-    hipLaunchKernelGGL(ag_fold_kernel, dim3((ncol + 63) / 64), dim3(AG_THREADS), 0, (hipStream_t)stream, rows, ncol, part,
-                       out);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return col_sums(part, rows, (size_t)ncol, 4, out, -1.0, (hipStream_t)stream);
 }
 
 extern "C" int apn_ag_combine_fwd(int b, int n, int s, int k, int o, const float *pq, const int *idx, const int *fps_idx,

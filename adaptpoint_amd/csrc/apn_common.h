@@ -146,6 +146,12 @@ inline hipError_t set_dyn_lds(DynLdsOnce &once, const void *fn, int bytes) {
     return hipSuccess;
 }
 
+// out[col] = the column sums of part[rows][ncol] in the shared order of include/adaptpoint_amd.h ("Partial-row folds") at
+// `lanes` in {4, 8, 16} row lanes; tail_count >= 0 also writes out[ncol] = tail_count, out[ncol + 1] = 1.  One launch;
+// instantiated for (double, double), (float, double) and (float, float): csrc/col_sums.hip.
+template <typename TIn, typename TOut>
+int col_sums(const TIn *part, int rows, size_t ncol, int lanes, TOut *out, double tail_count, hipStream_t s);
+
 }  // namespace apn
 
 #define APN_LAUNCH_CHECK()                                   \

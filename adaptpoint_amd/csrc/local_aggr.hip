@@ -17,7 +17,8 @@
 //                 wave): the extremum and the slot that holds it, and -- training -- ysum[q] = sum_k y[q,k] (the
 //                 backward pass and BatchNorm's mean need it) and the query's share of sum y^2, multiplicity-weighted,
 //                 float32 over the query's 32 positions, float64 across queries.  One float64 partial row per
-//                 workgroup, summed by la_stats_fold in a fixed order.
+//                 workgroup; apn_la_stats_fold adds them with the {count, 1} tail apn_sa_bn_fold takes (the fold is
+//                 csrc/col_sums.hip's, at 4 lanes).
 //   la_pool_bwd   one wave per point n: dL/dU[n] = the gradients of the (query, channel) pairs that selected n --
 //                 its rows walked through the index stage's inverse map (pcnt / poff / plist, ascending: a fixed
 //                 order, no float atomics) -- plus BatchNorm's dense term D y + E summed over the positions that
@@ -155,21 +156,6 @@ __global__ __launch_bounds__(256) void la_pool_fwd_kernel(long long nq, int n, f
     __syncthreads();
     for (int col = threadIdx.x; col < 2 * H; col += 256)
         part[(size_t)blockIdx.x * 2 * H + col] = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
-}
-
-// sums[2H + 2] = {column sums of part[rows][2H] in a fixed order, count, 1}: the form apn_sa_bn_fold takes (and the
-// SyncBatchNorm exchange all-reduces).  Grid: 2H / 64 workgroups of 256 threads (column, row group).
-__global__ __launch_bounds__(256) void la_stats_fold_kernel(const double *__restrict__ part, int rows, int ncol,
-                                                            double count, double *__restrict__ sums) {
-    __shared__ double red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, col = blockIdx.x * 64 + tx;
-    double s = 0.0;
-    if (col < ncol)
-        for (int r = ty; r < rows; r += 4) s += part[(size_t)r * ncol + col];
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && col < ncol) sums[col] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { sums[ncol] = count; sums[ncol + 1] = 1.0; }
 }
 
 __device__ __forceinline__ float la_wave_sum(float v) {
@@ -314,10 +300,7 @@ extern "C" int apn_la_stats_fold(const double *part, int rows, int c, double cou
     if (rows < 0 || c <= 0 || !(count >= 0.0)) return APN_EINVAL;
     if (rows == 0) return APN_OK;
     if (!part || !sums) return APN_EINVAL;
-    hipLaunchKernelGGL(la_stats_fold_kernel, dim3((2 * c + 63) / 64), dim3(256), 0, (hipStream_t)stream, part, rows,
-                       2 * c, count, sums);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return col_sums(part, rows, (size_t)2 * c, 4, sums, count, (hipStream_t)stream);
 }
 
 extern "C" int apn_la_pool_bwd(int b, int n, int c, int nsample, float radius, const float *gsel, const void *sel,

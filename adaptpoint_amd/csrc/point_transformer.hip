@@ -17,9 +17,9 @@
 //                    C -> C' and C' -> C' products read their vectors from LDS and their matrix rows coalesced.
 //
 // Every sum has a fixed order (thread-sequential, then the groups of a workgroup ascending, then apn_pt_fold over the
-// workgroups in its own fixed order; list walks ascending): two runs give the same bits.  No atomics, no memset, every output
-// element is written.  fp32 VALU arithmetic; the unit is built with -ffp-contract=off, the fma calls below are the
-// only fused operations.
+// workgroups -- the fold is csrc/col_sums.hip's, at 16 lanes; list walks ascending): two runs give the same bits.  No
+// atomics, no memset, every output element is written.  fp32 VALU arithmetic; the unit is built with
+// -ffp-contract=off, the fma calls below are the only fused operations.
 #include "apn_common.h"
 
 namespace apn {
@@ -103,27 +103,6 @@ __global__ __launch_bounds__(PT_THREADS) void pt_rel_stats_kernel(int n, int k, 
     if (tid < CL) {
         part[(size_t)blockIdx.x * 2 * C + c] = s;
         part[(size_t)blockIdx.x * 2 * C + C + c] = s2;
-    }
-}
-
-// sums[j] = the rows of part[rows][width] added up: 16 columns x 16 row lanes per workgroup; lane l adds the rows
-// l, l + 16, ... in ascending order, then the 16 lanes' sums are added in ascending lane order -- a fixed order
-constexpr int PT_FOLD_COLS = 16, PT_FOLD_LANES = PT_THREADS / PT_FOLD_COLS;
-__global__ __launch_bounds__(PT_THREADS) void pt_fold_kernel(const double *__restrict__ part, int rows, int width,
-                                                             double *__restrict__ sums) {
-    __shared__ double red[PT_THREADS];
-    const int tid = threadIdx.x, col = tid % PT_FOLD_COLS, lane = tid / PT_FOLD_COLS;
-    const int j = blockIdx.x * PT_FOLD_COLS + col;
-    double s = 0.0;
-    if (j < width) {
-#pragma unroll 4
-        for (int r = lane; r < rows; r += PT_FOLD_LANES) s += part[(size_t)r * width + j];
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (lane == 0 && j < width) {
-        for (int l = 1; l < PT_FOLD_LANES; ++l) s += red[l * PT_FOLD_COLS + col];
-        sums[j] = s;
     }
 }
 
@@ -691,10 +670,7 @@ extern "C" int apn_pt_fold(const double *part, int rows, int width, double *sums
     if (rows < 0 || rows > PT_ROWS_MAX || width < 0 || width > (1 << 20)) return APN_EINVAL;
     if (width == 0) return APN_OK;
     if (!sums || (rows > 0 && !part)) return APN_EINVAL;
-    hipLaunchKernelGGL(pt_fold_kernel, dim3((width + PT_FOLD_COLS - 1) / PT_FOLD_COLS), dim3(PT_THREADS), 0,
-                       (hipStream_t)stream, part, rows, width, sums);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return col_sums(part, rows, (size_t)width, 16, sums, -1.0, (hipStream_t)stream);
 }
 
 static int pt_colsum_rows(int n) {

@@ -7,7 +7,8 @@
 //     y_b  (O x N) = W   (O x C) x_b  (C x N)          forward
 //     gx_b (C x N) = W^T (C x O) gy_b (O x N)          gradient w.r.t. the input
 //     gW   (O x C) = sum_b gy_b (O x N) x_b^T (N x C)   gradient w.r.t. the weight (split over (b, position) ranges,
-//                                                       the shares added in a fixed order: reproducible)
+//                                                       the shares added in a fixed order: reproducible; the
+//                                                       fold is csrc/col_sums.hip's, at 4 lanes)
 // by describing each operand as "k-contiguous" (element (i, k) at i * ld + k) or "row-contiguous" (k * ld + i):
 // the float32 operands are read exactly as they lie in HBM (no transposed copies, no NHWC detour), split into two
 // or three bf16 planes on the way into LDS (three or six MFMAs per product: ~4e-6 of an fp32 contraction, or
@@ -837,22 +838,10 @@ __global__ __launch_bounds__(1024) void pw_bwd_fused_kernel(int B, int C, int N,
     }
 }
 
-// out[e] = sum_s part[s][e] in a fixed order: 64 elements x 4 interleaved split lanes per workgroup
-__global__ __launch_bounds__(256) void pw_fold_kernel(const float *__restrict__ part, int splits, size_t n,
-                                                      float *__restrict__ out) {
-    __shared__ double red[4][64];
-    const size_t e = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
-    const int q = threadIdx.x >> 6;
-    double s = 0.0;
-    if (e < n)
-        for (int k = q; k < splits; k += 4) s += (double)part[(size_t)k * n + e];
-    red[q][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (q == 0 && e < n) out[e] = (float)((red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
-}
-
-// pw_fold_kernel for the two blocks of apn_pw_contract2 in one launch (blockIdx.y picks the block), each folded in
-// pw_fold_kernel's order into an (r x q) block of a wider matrix: out[i * ldo + j] = sum_s part[s][i][j]
+// The split-K shares of one product, scratch [splits][n] -> out[n], are folded by csrc/col_sums.hip at 4 lanes (float64
+// sums, rounded to float32 once).  pw_fold2_kernel: that fold for the two blocks of apn_pw_contract2 in one launch
+// (blockIdx.y picks the block), each into an (r x q) block of a wider matrix: out[i * ldo + j] = sum_s part[s][i][j].
+// Its order is col_sums' at four lanes.
 struct PwFold2 {
     const float *part[2];
     float *out[2];
@@ -1150,11 +1139,7 @@ extern "C" int apn_pw_conv_grad_weight(int b, int c_in, int c_out, int n, int pr
     g.a_vec = pw_vec(gy, g.A.batch, n, n, c_out); g.b_vec = pw_vec(x, g.B.batch, n, n, c_in);
     PW_LAUNCH(true, true, dim3((c_in + PW_T - 1) / PW_T, (c_out + PW_T - 1) / PW_T, s), g);
     APN_LAUNCH_CHECK();
-    const size_t ne = (size_t)c_out * c_in;
-    hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)((ne + 63) / 64)), dim3(256), 0, (hipStream_t)stream, scratch, s,
-                       ne, gw);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return col_sums((const float *)scratch, s, (size_t)c_out * c_in, 4, gw, -1.0, (hipStream_t)stream);
 }
 
 extern "C" int apn_pw_conv_max_tiles(int n) { return (n + apn::PW_T - 1) / apn::PW_T; }
@@ -1240,12 +1225,7 @@ extern "C" int apn_pw_contract(int nbatch, int r, int q, int k, const float *a, 
     else if (a_kcont) PW_LAUNCH(true, false, grid, g);
     else if (b_kcont) PW_LAUNCH(false, true, grid, g);
     else PW_LAUNCH(false, false, grid, g);
-    if (splits > 0) {
-        const size_t ne = (size_t)r * q;
-        hipLaunchKernelGGL(pw_fold_kernel, dim3((unsigned)((ne + 63) / 64)), dim3(256), 0, (hipStream_t)stream, scratch,
-                           splits, ne, d);
-        APN_LAUNCH_CHECK();
-    }
+    if (splits > 0) return col_sums((const float *)scratch, splits, (size_t)r * q, 4, d, -1.0, (hipStream_t)stream);
     return APN_OK;
 }
 

@@ -17,8 +17,8 @@
 // the weights are wave-uniform (scalar loads), C/4 accumulators per lane.  The softmax and the pooled sum are
 // butterflies over the Kp lanes of a point (the same bits in every lane, an order fixed by Kp alone).
 //
-// Sums that cross workgroups are per-workgroup partial rows added in ascending row order by a second kernel: no
-// atomics, no memset, no workgroup waits for another; two runs give the same bits.
+// Sums that cross workgroups are per-workgroup partial rows added by a second launch (the fold is csrc/col_sums.hip's,
+// at 8 lanes, float64 out): no atomics, no memset, no workgroup waits for another; two runs give the same bits.
 #include "apn_common.h"
 
 namespace apn {
@@ -104,25 +104,6 @@ __global__ __launch_bounds__(RL_THREADS) void rl_moments_kernel(long long pairs,
         double v = red[0][threadIdx.x];
         for (int w = 1; w < RL_THREADS / 64; ++w) v += red[w][threadIdx.x];
         part[(size_t)blockIdx.x * RL_MOM + threadIdx.x] = v;
-    }
-}
-
-// sums[col] (float64) = the rows of part[rows][width] added up: a workgroup takes 32 columns, its eight slices the rows
-// s, s + 8, ... in ascending order, then the slices ascending -- an order fixed by (rows, width).
-template <typename T>
-__global__ __launch_bounds__(RL_THREADS) void rl_rows_fold_kernel(const T *__restrict__ part, int rows, int width,
-                                                                  double *__restrict__ sums) {
-    __shared__ double red[RL_THREADS / 32][32];
-    const int lane = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + lane;
-    double v = 0.0;
-    if (col < width)
-        for (int r = slice; r < rows; r += RL_THREADS / 32) v += (double)part[(size_t)r * width + col];
-    red[slice][lane] = v;
-    __syncthreads();
-    if (slice == 0 && col < width) {
-        for (int w = 1; w < RL_THREADS / 32; ++w) v += red[w][lane];
-        sums[col] = v;
     }
 }
 
@@ -513,10 +494,7 @@ extern "C" int apn_rl_moments(int b, int n, int k, const float *coords, const in
     hipLaunchKernelGGL(rl_moments_kernel, dim3(rows), dim3(RL_THREADS), 0, (hipStream_t)stream, (long long)b * n * k, n,
                        k, coords, idx, dist, sqrt_dist, part);
     APN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rl_rows_fold_kernel<double>, dim3((RL_MOM + 31) / 32), dim3(RL_THREADS), 0, (hipStream_t)stream,
-                       (const double *)part, rows, RL_MOM, mom);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return col_sums((const double *)part, rows, (size_t)RL_MOM, 8, mom, -1.0, (hipStream_t)stream);
 }
 
 extern "C" int apn_rl_fold(int c, const double *mom, double count, const float *w, const float *bias,
@@ -564,9 +542,7 @@ extern "C" int apn_rl_finalize(int c, int rows, const float *part, const double 
     if (!rl_width_ok(c) || rows < 0 || rows > 1024 || !(count >= 1.0)) return APN_EINVAL;
     if (!w || !stat || !sums || !grads || (rows > 0 && !part) || (training && !mom)) return APN_EINVAL;
     const int outs = c * c + c, width = c * c + c * (RL_E + 1);
-    hipLaunchKernelGGL(rl_rows_fold_kernel<float>, dim3((width + 31) / 32), dim3(RL_THREADS), 0, (hipStream_t)stream, part,
-                       rows, width, sums);
-    APN_LAUNCH_CHECK();
+    if (const int e = col_sums(part, rows, (size_t)width, 8, sums, -1.0, (hipStream_t)stream)) return e;
     hipLaunchKernelGGL(rl_finalize_kernel, dim3((outs + RL_THREADS - 1) / RL_THREADS), dim3(RL_THREADS), 0,
                        (hipStream_t)stream, c, (const double *)sums, mom, count, w, bias, gamma, stat, training, grads);
     APN_LAUNCH_CHECK();

@@ -51,6 +51,15 @@ APN_API const char *apn_error_string(int code);
  * keeps compiler-made packed-FP32 out), and the loader checks for them. */
 APN_API const char *apn_build_flags(void);
 
+/* Partial-row folds.  A reduction that crosses workgroups leaves one partial row per workgroup, part[rows][ncol], and a
+ * second launch adds the rows column by column (apn_la_stats_fold, apn_ag_fold, apn_pt_fold, the split-K shares of
+ * apn_pw_contract / apn_pw_contract2 / apn_pw_conv_grad_weight, apn_rl_moments, apn_rl_finalize).  They all add in ONE
+ * order (csrc/col_sums.hip), fixed by rows and a lane count L in {4, 8, 16} that each entry states:
+ *   partial rows are added by L lanes per column: lane l adds the rows l, l + L, l + 2L, ... in ascending order into one
+ *   float64 accumulator that starts at +0; the L sums are then combined by an adjacent-pair tree, (0+1), (2+3), ...,
+ *   then pairs of those, and so on.  A float32 result is the float64 total rounded once.
+ * No atomics: two runs give the same bits, and so does a replay from a captured graph.  rows == 0 gives zeros. */
+
 /* Replaces furthest_point_sampling_wrapper (pointnet2_api.cpp:18,
  * sampling.cpp:39-48 -> sampling_gpu.cu:101-260).
  *   xyz  (B,N,3) in; temp (B,N) in/out, pre-filled by the caller (1e10,
@@ -634,7 +643,7 @@ APN_API int apn_sa_wide_colsum_f32(const float *part, int rows, int ncol, float 
  *   values fit one workgroup's registers (b * n <= 32768, n % 4 == 0), else two.
  * conv_grad_input: gx (B,c_in,N) = w^T gy.   conv_grad_weight: gw (c_out,c_in) = sum_b gy_b x_b^T, split over
  *   apn_pw_conv_grad_weight_splits(...) ranges of (cloud, position) whose shares (scratch [splits][c_out][c_in])
- *   are added in a fixed order: bit-reproducible. */
+ *   are added in the shared order at 4 lanes ("Partial-row folds", above): bit-reproducible. */
 APN_API int apn_pw_conv_tiles(int b, int n);
 APN_API int apn_pw_conv_forward(int b, int c_in, int c_out, int n, int precision, const float *x, const float *w,
                                 float *y, float *part, void *stream);
@@ -654,7 +663,7 @@ APN_API int apn_pw_conv_grad_weight(int b, int c_in, int c_out, int n, int preci
  * the fused set-abstraction blocks (conv1 at the points, dL/df, dL/dW1 of the wide blocks):
  *   splits == 0: d[z] (r x q, ldd >= q) = a[z] (r x k) b[z] (k x q), z < nbatch (a batch stride of 0 shares the operand);
  *   splits  > 0: d (r x q, ldd == q) = sum_z a[z] b[z] in `splits` shares (apn_pw_contract_splits; scratch
- *                [splits][r][q]) added in a fixed order.
+ *                [splits][r][q]) added in the shared order at 4 lanes ("Partial-row folds", above).
  * a_kcont / b_kcont: the operand's element (i, k) lies at i * ld + k (1) or at k * ld + i (0). */
 APN_API int apn_pw_contract_splits(int nbatch, int r, int q, int k);
 APN_API int apn_pw_contract(int nbatch, int r, int q, int k, const float *a, long long a_batch, int lda, int a_kcont,
@@ -664,7 +673,7 @@ APN_API int apn_pw_contract(int nbatch, int r, int q, int k, const float *a, lon
  * of both problems' 128 x 128 tile grids, the problem picked from the workgroup index.  Every array argument has two
  * entries, problem p described as for apn_pw_contract.  splits[p] == 0 for both: d[p][z] = a[p][z] b[p][z] with leading
  * dimension ldd[p].  splits[p] > 0 for both (apn_pw_contract2_splits(p, ...)): d[p] = sum_z a[p][z] b[p][z] in
- * splits[p] shares (scratch[p]: [splits[p]][r][q]) added in a fixed order by one fold launch that writes the r x q result
+ * splits[p] shares (scratch[p]: [splits[p]][r][q]) added in that order by one fold launch that writes the r x q result
  * with leading dimension ldd[p] >= q[p] -- the two results may be column blocks of one matrix.  The fast loaders need
  * 16-byte aligned operand origins, rows and batch strides; anything else takes the value-by-value loads (correct, slower).
  * For pairs that each fill less than the chip (the hoisted feature-propagation block, csrc/feature_prop.hip). */
@@ -862,7 +871,8 @@ APN_API int apn_spectral_norm_grad_many(int n_layers, const int *rows, const int
  *   pool_fwd: ext (b,n,c) = ext_k y[q,k] (max where gamma >= 0, min elsewhere; gamma NULL: max), sel (b,n,c) uint8 = the
  *     slot that holds it; training (ysum and part both given): ysum (b,n,c) = sum_k y[q,k] and
  *     part[apn_la_pool_rows(b, n)][2c] (float64) = the workgroups' shares of {sum y, sum y^2} over the b*n*32 positions.
- *   stats_fold: sums[2c + 2] (float64) = {the shares added in a fixed order, count, 1}: apn_sa_bn_fold's `sums`.
+ *   stats_fold: sums[2c + 2] (float64) = {the shares added in the shared order at 4 lanes ("Partial-row folds", above),
+ *     count, 1}: apn_sa_bn_fold's `sums`.  rows == 0 returns before it writes.
  *   pool_bwd: gsel (b,n,c) = the gradient at the selected positions (apn_sa_wide_bwd_prep's goa), de = {D[c], E[c]}
  *     (apn_sa_wide_consts2: BatchNorm's dense term dL/dy = D y + E), tmap / pcnt_poff / plist / geo: the NeighbourIndex
  *     of idx (apn_sa_wide_tilemap, apn_sa_wide_csr) -> dU (b,n,c) = dL/dU summed per point in a fixed order (no float
@@ -1092,8 +1102,8 @@ APN_API int apn_po_aggregation_bwd(int n, int m, int k, int c, int w_c, const fl
  *   rows: how many partial rows (workgroups) the strided kernels write: apn_pt_rows(n, k, c) = ceil(n k / 64), at most
  *     2048 (c <= 64), 1024 (c = 128), 256 (c = 256) or 128 (c = 512); 0 for n == 0 or refused arguments.
  *   rel_stats: part[rows][2c] (float64) = the workgroups' shares of {sum r, sum r^2} over the n k positions.
- *   fold: sums[width] (float64) = the rows of part[rows][width] added in a fixed order (16 interleaved ascending runs,
- *     then the runs ascending); rows <= 2048, width <= 2^20.
+ *   fold: sums[width] (float64) = the rows of part[rows][width] added in the shared order at 16 lanes ("Partial-row
+ *     folds", above); rows <= 2048, width <= 2^20.
  *   mid: t (n,k,c'); part given: part[apn_pt_mid_rows(n, k, c)][2c'] (float64) = the shares of {sum t, sum t^2}, one row per
  *     workgroup: a workgroup per tile of 8192 / c positions, at most apn_pt_rows(n, k, c).
  *   attend: a (n,k,c') and out (n,c).
@@ -1180,7 +1190,8 @@ APN_API int apn_vg_mean_bwd(int n, int m, int c, const float *grad_out, const in
  * e = [p_n, p_j, p_n - p_j, dist] (10 wide).  Shapes: b >= 0 (0: nothing is launched), n >= 1, 1 <= k <= 32,
  * b n < 2^24, c in {8, 16, 32, 64, 128}; anything else is APN_EINVAL before a launch.
  *   moments: mom[65] (float64) = {sum e_i (10), sum e_i e_j for i <= j (55, row-major upper triangle)} over the b n k
- *     pairs; part[apn_rl_moment_rows(b, n, k)][65] (float64) is the workgroups' shares, added in ascending order.
+ *     pairs; part[apn_rl_moment_rows(b, n, k)][65] (float64) is the workgroups' shares, added in the shared order at 8
+ *     lanes ("Partial-row folds", above).
  *   fold: w (c,10), bias (c or NULL): the convolution; gamma, beta (c or NULL), eps, momentum: its BatchNorm; count =
  *     b n k.  training != 0: batch mean = w.mu + bias and biased variance = w^T Sigma w from mom; running_mean /
  *     running_var (both or neither) take (1 - momentum) old + momentum new, the variance unbiased, and
@@ -1192,7 +1203,7 @@ APN_API int apn_vg_mean_bwd(int n, int m, int c, const float *grad_out, const in
  *     pooled (b,c,n): pooled[c1,n] = sum_k softmax_k((A_hh h_k)[c1]) h_k[c1].
  *   backward: a (c,c) = A_hh, at its transpose, dpooled (b,c,n); part[apn_rl_bwd_rows(b, n, k, c)][c c + 11 c]
  *     (float32): per workgroup the shares of dA_hh and, per channel, of {sum dy (e - mu)_0..9, sum dy}.
- *   finalize: rows = apn_rl_bwd_rows(...); sums[c c + 11 c] (float64): scratch, the rows added in ascending order;
+ *   finalize: rows = apn_rl_bwd_rows(...); sums[c c + 11 c] (float64): scratch, the rows added in the shared order at 8 lanes;
  *     grads[c c + 13 c] (float32) = dA_hh | dgamma | dbeta | dW (c,10) | dbias (dbias is an exact zero when training != 0).  No gradient flows to coords, dist or idx.
  * Every sum has an order fixed by the shapes: two runs give the same bits.  No atomics, no memset. */
 APN_API int apn_rl_moment_rows(int b, int n, int k);
@@ -1221,8 +1232,8 @@ APN_API int apn_rl_finalize(int c, int rows, const float *part, const double *mo
  * position s k + slot.  Everything fp32 / int32 and contiguous; element offsets are 64-bit inside the kernels.
  *   moments: part [apn_ag_moment_rows(s)][b][2] = float64 {sum d, sum d^2} of each workgroup's queries (d rounded to
  *     fp32 as the subtraction gives it, squared and added in float64); apn_ag_fold(rows, 2 b) gives the (b,2) moments.
- *   fold: out[col] = the sum of part[rows][ncol] (float64) over the rows: ascending inside four equal row ranges, the
- *     ranges then added in order.
+ *   fold: out[col] = the sum of part[rows][ncol] (float64) over the rows, in the shared order at 4 lanes ("Partial-row
+ *     folds", above).
  *   combine_fwd: r (b) and c0 (o) are INPUT arrays.  v = ((r * (P[j] - P[a])) + Q[a]) + c0, each operation rounded.
  *     training != 0: y and part are written -- part [apn_pw_conv_tiles(b, s k)][2][o], BatchNorm's partial statistics in
  *       the layout apn_pw_bn_act folds ({sum, M2 around the tile's own mean} per 128 positions of a cloud).

@@ -136,7 +136,7 @@ def coverage():
         for planes in (2, 3):
             cov[(form_of(c), loader_class(c, synthetic_ptrs(c)), planes)].append(c.name)
         if c.reduce:
-            cov[("fold", "pw_fold_kernel")].append(c.name)
+            cov[("fold", "col_sums_kernel")].append(c.name)
             for tag in ("split-empty", "split-straddle", "split-renumbered"):
                 if tag in c.name:
                     cov[(form_of(c), tag)].append(c.name)

@@ -40,7 +40,7 @@ def test_every_loader_class_and_layout_form_is_in_the_table():
     want = [(CC._form_name(f), cls, planes) for f in CC.FORMS for cls in CC.CLASSES for planes in (2, 3)]
     want += [(CC._form_name(f), tag) for f in CC.FORMS
              for tag in ("renumbered grid", "plain grid", "split-empty", "split-straddle", "split-renumbered")]
-    want += [("fold", "pw_fold_kernel"), ("fold", "pw_fold2_kernel"), ("pair", "direct")]
+    want += [("fold", "col_sums_kernel"),("fold", "pw_fold2_kernel"), ("pair", "direct")]
     for key in want:
         assert cov[key], key
 
