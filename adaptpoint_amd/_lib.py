@@ -167,6 +167,12 @@ SIGNATURES = {
     "apn_cloud_transform": [_c_int] * 4 + [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 8,
     "apn_cls_confusion": [_c_int] * 2 + [_c_void_p, _c_int] + [_c_void_p] * 5,
     "apn_part_ious": [_c_int] * 5 + [_c_void_p] * 13,
+    "apn_ss_max_classes": [],
+    "apn_ss_confusion": [_c_int] * 3 + [_c_void_p] * 2 + [_c_int] * 2 + [_c_void_p] * 4,
+    "apn_ss_votes_add": [_c_int] * 3 + [_c_void_p] * 2 + [_c_int] + [_c_void_p] * 5,
+    "apn_ss_votes_finish": [_c_int] * 2 + [_c_void_p] * 3 + [_c_int] * 2 + [_c_void_p] * 4,
+    "apn_ss_project": [_c_int] * 3 + [_c_void_p] * 4 + [_c_int] * 2 + [_c_void_p] * 5,
+    "apn_ss_crop_nearest": [_c_int] * 3 + [_c_void_p] * 6,
     "apn_la_pool_rows": [_c_int] * 2,
     "apn_la_pool_fwd": [_c_int] * 4 + [_c_float] + [_c_void_p] * 3 + [_c_int] + [_c_void_p] * 7,
     "apn_la_stats_fold": [_c_void_p, _c_int, _c_int, _c_double, _c_void_p, _c_void_p],

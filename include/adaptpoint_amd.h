@@ -818,6 +818,45 @@ APN_API int apn_part_ious(int b, int c, int n, int s, int nparts, const float *l
                           const int *part_offset, const int *part_ids, const int *valid, float *ious, float *cls_sum,
                           int *cls_num, double *ins_sum, int *ins_num, int *rejected, void *stream);
 
+/* Scene segmentation's per-point work outside the network (csrc/scene_seg.hip; the reference's
+ * examples/segmentation/main.py and crop_pc of openpoints/dataset/data_util.py).  No host read in any entry, no float
+ * atomics, integer atomics only where their order cannot matter: the same bits on every run.  Every index read from a
+ * tensor is range-checked before it addresses anything.  c <= apn_ss_max_classes() = 64 wherever counters are kept.
+ *
+ * Counters `cm`: c*c + 1 unsigned 64-bit cells, added to and never cleared: cell t*c + p for target t and prediction p;
+ *   a target equal to ignore_index (when has_ignore != 0) is skipped; any other target outside [0, c) adds to the last
+ *   cell.  Predictions follow torch.argmax: the first channel of the maximum, a NaN beats every number.
+ *
+ * apn_ss_confusion: logits (b, c, n) float32 contiguous, target (b, n) int32, valid a device int32 scalar or NULL
+ *   (clouds at or beyond clamp(*valid, 0, b) are not counted), pred (b, n) int32 or NULL (written for every cloud).
+ * apn_ss_votes_add: one sub-cloud's logits (c, n_part) and rows idx (n_part): acc[idx[j], :] += logits[:, j] (acc (n, c)
+ *   float32), cnt[idx[j]] += 1, by plain loads and stores; `call` >= 1 numbers the calls of one scene, stamp (n) int32
+ *   starts at 0.  A row that occurs twice in one call is added once and counted in flags[0]; a row outside [0, n) is
+ *   skipped and counted in flags[1].  A point's sum is the sequence of fp32 adds in call order.
+ * apn_ss_votes_finish: mean (n, c) = acc / max(cnt, 1) (one correctly rounded division), pred (n) its argmax, both may
+ *   be NULL; with labels (n) int32 the counters are added to.
+ * apn_ss_project: logits (c, m) per voxel column, slot (m): voxel v's column, voxel_of (n): pred_voxel (m, scratch,
+ *   written) = argmax of column slot[v], pred (n, may be NULL) = pred_voxel[voxel_of[i]], counters against labels (n, may
+ *   be NULL).  A slot or voxel outside [0, m) is counted in flags[1]; its points get pred -1 and no count.
+ * apn_ss_crop_nearest: coord (n, 3) float32, offset (b) int32 cumulative ends, centre (b) int32 a row inside each cloud:
+ *   idx (b, k) int32 = the global rows of the k nearest rows of the centre in ascending row, the set
+ *   argsort(d, stable)[:k] for d = (dx*dx + dy*dy) + dz*dz rounded after every operation.  stats[0] counts rows with a
+ *   non-finite coordinate, stats[1] clouds that were refused and left unwritten (bad offsets, centre outside the cloud,
+ *   fewer than k rows).  One workgroup per cloud.
+ * A size outside its range or a missing pointer -> APN_EINVAL before any launch; empty work -> APN_OK. */
+APN_API int apn_ss_max_classes(void);
+APN_API int apn_ss_confusion(int b, int c, int n, const float *logits, const int *target, int ignore_index,
+                             int has_ignore, const int *valid, unsigned long long *cm, int *pred, void *stream);
+APN_API int apn_ss_votes_add(int n, int c, int n_part, const float *logits, const int *idx, int call, float *acc,
+                             int *cnt, int *stamp, int *flags, void *stream);
+APN_API int apn_ss_votes_finish(int n, int c, const float *acc, const int *cnt, const int *labels, int ignore_index,
+                                int has_ignore, unsigned long long *cm, float *mean, int *pred, void *stream);
+APN_API int apn_ss_project(int c, int m, int n, const float *logits, const int *slot, const int *voxel_of,
+                           const int *labels, int ignore_index, int has_ignore, int *pred_voxel,
+                           unsigned long long *cm, int *pred, int *flags, void *stream);
+APN_API int apn_ss_crop_nearest(int b, int n, int k, const float *coord, const int *offset, const int *centre,
+                                int *idx, int *stats, void *stream);
+
 /* The last layer of the discriminator's group-all stage with its pooling
  * (openpoints/models_adaptpoint/point_discriminator.py:183-189: conv -> ReLU -> max over the cloud's points), fused:
  *   out (B,c_out) = [relu](max_n (w x_b)[o][n] + bias[o]),  idx (B,c_out) int32 = the position of that maximum (the
