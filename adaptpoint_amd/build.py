@@ -19,7 +19,7 @@ OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libadaptpoint_amd.so")
 ARCH = "gfx950"
 SOURCES = ["capi.hip", "fps.hip", "ball_query.hip", "group_points.hip", "interpolate.hip", "sa_fused.hip", "sa_glue.hip", "sa_seq.hip", "sa_geo.hip", "sa_wide.hip", "sa_wide_glue.hip", "sa_wide_dense.hip", "pointwise.hip", "feature_prop.hip", "spectral.hip", "augment.hip", "pointset_group.hip", "attention.hip", "token_attention.hip", "online_aug.hip", "cloud_transform.hip", "cls_metrics.hip", "part_metrics.hip", "local_aggr.hip", "knn.hip", "edge_conv.hip", "chamfer.hip", "emd.hip", "pointops.hip", "point_transformer.hip", "voxel_grid.hip", "randla.hip", "affine_group.hip", "depth_views.hip", "col_sums.hip", "scene_seg.hip"]
-HEADERS = ["apn_common.h", "apn_mfma.h", "sa_chain.h", "ball_query_body.h", "anchor_rotation.h", "lds_bitonic.h", "knn_list.h",
+HEADERS = ["apn_common.h", "apn_mfma.h", "sa_chain.h", "ball_query_body.h", "anchor_rotation.h", "lds_bitonic.h", "knn_list.h", "tile_map.h", "reverse_lists.h",
            os.path.join("..", "..", "include", "adaptpoint_amd.h")]
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
             "-fvisibility=hidden", "-Wall", "-Wno-unused-command-line-argument"] + os.environ.get("APN_EXTRA_CXXFLAGS", "").split()

@@ -31,6 +31,7 @@
 //                 [du | dv] of pitch 2H: dL/dx = [Wa - Wb ; Wb]^T [du | dv]^T and the weight gradients are
 //                 contractions of that one buffer.
 #include "apn_common.h"
+#include "reverse_lists.h"
 
 namespace apn {
 
@@ -215,11 +216,7 @@ __global__ __launch_bounds__(256) void ec_bwd_prep_kernel(int n, int H, const fl
 }
 
 // ------------------------------------------------------------------------------------------ reverse neighbours
-__global__ __launch_bounds__(256) void ec_csr_init_kernel(long long npts, int *__restrict__ pcnt) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e < npts) pcnt[e] = 0;
-}
-
+// (the init and scan kernels: csrc/reverse_lists.h)
 // mq: gathering rows per cloud (n for the EdgeConv graph; apn_po_csr: all m rows gather from one set of n)
 __device__ __forceinline__ long long ec_target(const int *__restrict__ idx, long long pos, int n, int mq, int K) {
     int nb = idx[pos];
@@ -236,36 +233,6 @@ __global__ __launch_bounds__(256) void ec_csr_count_fill_kernel(long long npos, 
     const long long gj = ec_target(idx, pos, n, mq, K);
     if (!fill) atomicAdd(pcnt + gj, 1);
     else tmp[atomicAdd(cursor + gj, 1)] = (int)pos;
-}
-
-// one block per cloud: poff = cursor = (the cloud's first position) + exclusive scan of pcnt
-__global__ __launch_bounds__(1024) void ec_csr_scan_kernel(int n, int K, const int *__restrict__ pcnt,
-                                                           int *__restrict__ poff, int *__restrict__ cursor) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x, cloud = blockIdx.x, per = (n + 1023) / 1024;
-    const int *__restrict__ cnt = pcnt + (size_t)cloud * n;
-    int s = 0;
-    for (int i = 0; i < per; ++i) {
-        const int k = t * per + i;
-        if (k < n) s += cnt[k];
-    }
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = cloud * n * K + part[t] - s;
-    for (int i = 0; i < per; ++i) {
-        const int k = t * per + i;
-        if (k < n) {
-            poff[(size_t)cloud * n + k] = run;
-            cursor[(size_t)cloud * n + k] = run;
-            run += cnt[k];
-        }
-    }
 }
 
 // one wave per point: the list's entries (distinct positions, in the order the fill's atomics ran) ranked into place
@@ -466,49 +433,44 @@ extern "C" int apn_ec_bwd_prep_act(int b, int n, int c, const float *g, long lon
     return ec_bwd_prep_launch(b, n, c, g, gs_b, gs_c, gs_n, ext, pack, slope, gsel, part_s, stream);
 }
 
-extern "C" int apn_ec_csr(int b, int n, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream) {
-    if (!ec_sizes(b, n, k)) return APN_EINVAL;
-    if (b == 0 || n == 0) return APN_OK;
-    if (!idx || !pcnt_poff || !plist || !scratch) return APN_EINVAL;
-    const long long npts = (long long)b * n, npos = npts * k;            // < 2^30
+// The reverse lists of `clouds` sets of n points, each gathered by the mq k positions of its own rows: five launches.
+// scratch: clouds n + clouds mq k ints.  No position (mq == 0): every list is empty.
+static int ec_csr_launch(int clouds, int n, int mq, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch,
+                         hipStream_t st) {
+    const long long npts = (long long)clouds * n, npos = (long long)clouds * mq * k;
     int *pcnt = pcnt_poff, *poff = pcnt_poff + npts;
-    int *cursor = scratch, *tmp = scratch + npts;                        // scratch: b n (k + 1) ints
-    hipStream_t st = (hipStream_t)stream;
+    int *cursor = scratch, *tmp = scratch + npts;
     const unsigned pb = (unsigned)((npos + 255) / 256);
-    hipLaunchKernelGGL(ec_csr_init_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, npts, pcnt);
-    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, n, k, 0, idx, pcnt, cursor, tmp);
-    hipLaunchKernelGGL(ec_csr_scan_kernel, dim3(b), dim3(1024), 0, st, n, k, pcnt, poff, cursor);
-    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, n, k, 1, idx, pcnt, cursor, tmp);
+    if (npos == 0) {
+        hipLaunchKernelGGL(csr_init_kernel, dim3((unsigned)((2 * npts + 255) / 256)), dim3(256), 0, st, 2 * npts, pcnt,
+                           (int *)nullptr);
+        APN_LAUNCH_CHECK();
+        return APN_OK;
+    }
+    hipLaunchKernelGGL(csr_init_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, npts, pcnt, (int *)nullptr);
+    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, mq, k, 0, idx, pcnt, cursor, tmp);
+    hipLaunchKernelGGL(csr_scan_kernel, dim3(clouds), dim3(1024), 0, st, n, (const int *)nullptr, mq * k, pcnt, poff, cursor);
+    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, mq, k, 1, idx, pcnt, cursor, tmp);
     hipLaunchKernelGGL(ec_csr_sort_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, st, npts, pcnt, poff, tmp,
                        plist);
     APN_LAUNCH_CHECK();
     return APN_OK;
 }
 
-// The reverse lists of an (m, k) index into n rows (the stacked-cloud operators of csrc/pointops.hip): apn_ec_csr's five
-// launches over one "cloud" of n rows gathered by m k positions.  m == 0: every list is empty.
+extern "C" int apn_ec_csr(int b, int n, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream) {
+    if (!ec_sizes(b, n, k)) return APN_EINVAL;
+    if (b == 0 || n == 0) return APN_OK;
+    if (!idx || !pcnt_poff || !plist || !scratch) return APN_EINVAL;
+    return ec_csr_launch(b, n, n, k, idx, pcnt_poff, plist, scratch, (hipStream_t)stream);       // b n k < 2^30
+}
+
+// The reverse lists of an (m, k) index into n rows (the stacked-cloud operators of csrc/pointops.hip): one "cloud" of
+// n rows gathered by m k positions; scratch: n + m k ints.  m == 0: every list is empty.
 extern "C" int apn_po_csr(int n, int m, int k, const int *idx, int *pcnt_poff, int *plist, int *scratch, void *stream) {
     if (n < 0 || m < 0 || n >= (1 << 24) || m >= (1 << 24) || k < 1 || (long long)m * k >= (1ll << 31)) return APN_EINVAL;
     if (n == 0) return APN_OK;
     if (!idx || !pcnt_poff || !plist || !scratch) return APN_EINVAL;
-    const long long npos = (long long)m * k;
-    int *pcnt = pcnt_poff, *poff = pcnt_poff + n;
-    int *cursor = scratch, *tmp = scratch + n;                           // scratch: n + m k ints
-    hipStream_t st = (hipStream_t)stream;
-    if (m == 0) {
-        hipLaunchKernelGGL(ec_csr_init_kernel, dim3((unsigned)((2ll * n + 255) / 256)), dim3(256), 0, st, 2ll * n, pcnt);
-        APN_LAUNCH_CHECK();
-        return APN_OK;
-    }
-    const unsigned pb = (unsigned)((npos + 255) / 256);
-    hipLaunchKernelGGL(ec_csr_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (long long)n, pcnt);
-    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, m, k, 0, idx, pcnt, cursor, tmp);
-    hipLaunchKernelGGL(ec_csr_scan_kernel, dim3(1), dim3(1024), 0, st, n, k, pcnt, poff, cursor);
-    hipLaunchKernelGGL(ec_csr_count_fill_kernel, dim3(pb), dim3(256), 0, st, npos, n, m, k, 1, idx, pcnt, cursor, tmp);
-    hipLaunchKernelGGL(ec_csr_sort_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (long long)n, pcnt, poff, tmp,
-                       plist);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return ec_csr_launch(1, n, m, k, idx, pcnt_poff, plist, scratch, (hipStream_t)stream);
 }
 
 extern "C" int apn_ec_pool_bwd(int b, int n, int c, int k, const float *gsel, const void *sel, const int *pcnt_poff,

@@ -30,6 +30,7 @@
 // entries (apn_sa_wide_out, apn_sa_bn_fold, apn_sa_wide_bwd_prep, apn_sa_wide_consts2); the dense products run on
 // csrc/pointwise.hip's contraction kernel.
 #include "apn_common.h"
+#include "tile_map.h"
 
 namespace apn {
 
@@ -314,15 +315,13 @@ extern "C" int apn_la_pool_bwd(int b, int n, int c, int nsample, float radius, c
     if (!gsel || !sel || !tmap || !pcnt_poff || !plist || !geo || !U || !xyz || !de || !wp || !dU || !dT)
         return APN_EINVAL;
     const long long npts = (long long)b * n;
-    // the tile map's blob: [4, 4 + BM) tq0, rowinfo from 4 + BM rounded up to 4 (csrc/sa_wide_glue.hip)
-    const int *tq0 = tmap + 4;
-    const unsigned *rowinfo = (const unsigned *)(tmap + 4 + ((npts + 3) & ~3ll));
+    const TileMapView tm(tmap, (int)npts, b);           // (every point is a query: the map of b n queries)
     const dim3 grid((unsigned)((npts + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t)stream;
 #define APN_LA_BWD(VEC)                                                                                               \
     hipLaunchKernelGGL(la_pool_bwd_kernel<VEC>, grid, block, 0, st, npts, n, 1.0f / radius, gsel,                     \
-                       (const unsigned char *)sel, tq0, rowinfo, pcnt_poff, pcnt_poff + npts, plist, geo, U, xyz, ysum, \
-                       de, wp, ldw, dU, dT, dp)
+                       (const unsigned char *)sel, tm.tq0, tm.rowinfo, pcnt_poff, pcnt_poff + npts, plist, geo, U, xyz,   \
+                       ysum, de, wp, ldw, dU, dT, dp)
     switch (c / 64) {
         case 1: APN_LA_BWD(1); break;
         case 2: APN_LA_BWD(2); break;

@@ -49,6 +49,7 @@
 #include "apn_mfma.h"
 #include <type_traits>
 #include "sa_chain.h"
+#include "tile_map.h"
 
 namespace apn {
 
@@ -113,10 +114,10 @@ __device__ __forceinline__ void stamp(const SaArgs &a, int wave, int k) {
 __device__ __forceinline__ int tm_tiles(const SaArgs &a) { return a.tmap[0]; }
 __device__ __forceinline__ const int *tm_tq0(const SaArgs &a) { return a.tmap + 4; }
 __device__ __forceinline__ const unsigned *tm_rows(const SaArgs &a) {
-    return reinterpret_cast<const unsigned *>(a.tmap + 4 + ((a.b * a.m + 3) & ~3));
+    return tile_map_rowinfo(a.tmap, a.b * a.m);
 }
 __device__ __forceinline__ const int *tm_nn(const SaArgs &a) {
-    return a.tmap + 4 + ((a.b * a.m + 3) & ~3) + (size_t)32 * a.b * a.m;
+    return reinterpret_cast<const int *>(tm_rows(a)) + (size_t)32 * a.b * a.m;      // (behind rowinfo: tile_map.h)
 }
 __device__ __forceinline__ unsigned ri_q(unsigned info) { return info & 0xffu; }
 __device__ __forceinline__ unsigned ri_slot(unsigned info) { return (info >> 8) & 0xffu; }

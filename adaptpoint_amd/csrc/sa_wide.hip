@@ -32,6 +32,7 @@
 // (column block, 32-deep k chunk).
 #include "apn_common.h"
 #include "apn_mfma.h"
+#include "tile_map.h"
 #include <type_traits>
 
 namespace apn {
@@ -50,10 +51,10 @@ struct WideArgs {
 __device__ __forceinline__ int tm_tiles(const WideArgs &a) { return a.tmap[0]; }
 __device__ __forceinline__ const int *tm_tq0(const WideArgs &a) { return a.tmap + 4; }
 __device__ __forceinline__ const unsigned *tm_rows(const WideArgs &a) {
-    return reinterpret_cast<const unsigned *>(a.tmap + 4 + ((a.ntiles + 3) & ~3));
+    return tile_map_rowinfo(a.tmap, a.ntiles);
 }
 __device__ __forceinline__ const int *tm_nn(const WideArgs &a) {
-    return a.tmap + 4 + ((a.ntiles + 3) & ~3) + (size_t)32 * a.ntiles;
+    return tile_map_rownn(a.tmap, a.ntiles);
 }
 __device__ __forceinline__ int ri_q(unsigned info) { return (int)(info & 0xffu); }
 __device__ __forceinline__ int ri_slot(unsigned info) { return (int)((info >> 8) & 0xffu); }

@@ -7,6 +7,9 @@
 // dL/dW1 = G^T f, Qm = W2^T D2 W2, W2 Gram) stay library GEMMs in the caller.
 #include "apn_common.h"
 #include "apn_mfma.h"
+#include "lds_bitonic.h"
+#include "reverse_lists.h"
+#include "tile_map.h"
 
 namespace apn {
 
@@ -500,10 +503,10 @@ __global__ __launch_bounds__(256) void tilemap_fill_kernel(int b, int m, const u
         toff[c] = base_tile;
         if (c == b - 1) ntiles[0] = base_tile + tcount[c];
     }
-    // A wave writes the rows of sixteen queries, each half of it (32 lanes = the 32 slots) eight of them.  Round 5: every load
-    // the sixteen queries need -- count, packing record, the next query's record, the 32 neighbours -- is requested up front,
-    // unconditionally on clamped indices (one round trip; the tile's query count of a starting query: a second one).  The
-    // loop that stood here paid sixteen dependent round trips per wave with half the lanes returned: 48 of the stacked
+    // A wave writes the rows of sixteen queries, each half of it (32 lanes = the 32 slots) eight of them.  Every load the
+    // sixteen queries need -- count, packing record, the next query's record, the 32 neighbours -- is requested up front,
+    // unconditionally on clamped indices (one round trip; the tile's query count of a starting query: a second one).  A
+    // loop over the queries pays sixteen dependent round trips per wave with half the lanes returned: 48 of the stacked
     // launch's 55 us.
     const int lane = t & 63, w = t >> 6, l32 = lane & 31, half = lane >> 5;
     int cnv[8], nbv[8];
@@ -557,65 +560,28 @@ __global__ __launch_bounds__(256) void tilemap_fill_kernel(int b, int m, const u
 // Counting sort: count (integer atomics: the counts do not depend on the order), scan per cloud, fill
 // (order left to the atomics), then every list is sorted -- the result is a pure function of idx.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ const int *tm_toff(const int *tmap, int nq, int b) {
-    return tmap + 4 + ((nq + 3) & ~3) + (size_t)64 * nq + b;
-}
-
-// pcnt = 0 and (optional) fq = -1, one launch (a kernel, not hipMemsetAsync: the whole index stage must
-// replay from a captured hipGraph, and a captured memset node aborted the replay here)
-__global__ __launch_bounds__(256) void csr_init_kernel(long long npts, int *__restrict__ pcnt, int *__restrict__ fq) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= npts) return;
-    pcnt[e] = 0;
-    if (fq) fq[e] = -1;
-}
+// The init and scan kernels and the device pieces shared with the one-launch form below: csrc/reverse_lists.h.
 
 // one thread per row of the tile map.  fill = 0: count the rows of every point (and, with fidx, record which query
 // each sampled point is: fq[b n] -- FPS picks are distinct); fill = 1: write the row ids behind the cursors.
-__global__ __launch_bounds__(256) void csr_count_fill_kernel(int nq, int n, int m, int fill,
-                                                             const int *__restrict__ idx,
+__global__ __launch_bounds__(256) void csr_count_fill_kernel(int nq, int b, int n, int m, int fill,
                                                              const int *__restrict__ tmap, int *__restrict__ pcnt,
                                                              int *__restrict__ poff, int *__restrict__ plist,
                                                              const int *__restrict__ fidx, int *__restrict__ fq) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;       // row id
     const int tile = (int)(e >> 5);
     if (tile >= tmap[0]) return;
-    const unsigned info = reinterpret_cast<const unsigned *>(tmap + 4 + ((nq + 3) & ~3))[e];
+    const TileMapView tm(tmap, nq, b);
+    const unsigned info = tm.rowinfo[e];
     if (((info >> 16) & 0xffu) == 0) return;
-    const int q = tmap[4 + tile] + (int)(info & 0xffu);
+    const int q = tm.tq0[tile] + (int)(info & 0xffu);
     const size_t cbase = (size_t)(q / m) * n;
-    const size_t gn = cbase + tmap[4 + ((nq + 3) & ~3) + (size_t)32 * nq + e];           // rownn[e]
+    const size_t gn = cbase + tm.rownn[e];
     if (!fill) {
         atomicAdd(pcnt + gn, 1);
         if (fq && ((info >> 8) & 0xffu) == 0) fq[cbase + fidx[q]] = q % m;                 // one row per query has slot 0
     } else {
         plist[atomicAdd(poff + gn, 1)] = (int)e;
-    }
-}
-
-// one block per cloud: poff = (first row id of the cloud) + exclusive scan of pcnt
-__global__ __launch_bounds__(1024) void csr_scan_kernel(int nq, int b, int n, const int *__restrict__ tmap,
-                                                        const int *__restrict__ pcnt, int *__restrict__ poff) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x, cloud = blockIdx.x, per = (n + 1023) / 1024;
-    const int *__restrict__ cnt = pcnt + (size_t)cloud * n;
-    int s = 0;
-    for (int i = 0; i < per; ++i) {
-        const int k = t * per + i;
-        if (k < n) s += cnt[k];
-    }
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = tm_toff(tmap, nq, b)[cloud] * 32 + part[t] - s;
-    for (int i = 0; i < per; ++i) {
-        const int k = t * per + i;
-        if (k < n) { poff[(size_t)cloud * n + k] = run; run += cnt[k]; }
     }
 }
 
@@ -628,19 +594,13 @@ __global__ __launch_bounds__(1024) void csr_scan_kernel(int nq, int b, int n, co
 // Both leave the same ascending list; geo's sum order is fixed per kernel (so per list length): reproducible.
 constexpr int CSR_SHORT = 16, CSR_LONG = 2048;
 
-__device__ __forceinline__ void geo_add(const int *__restrict__ tmap, const unsigned *__restrict__ rows,
-                                        const float *__restrict__ new_xyz, int e, float &occ, float &sx, float &sy,
-                                        float &sz) {
-    const unsigned info = rows[e];
-    const float mult = (float)((info >> 16) & 0xffu);
-    const float *__restrict__ q = new_xyz + (size_t)(tmap[4 + (e >> 5)] + (int)(info & 0xffu)) * 3;
-    occ += mult;
-    sx = __builtin_fmaf(mult, q[0], sx);
-    sy = __builtin_fmaf(mult, q[1], sy);
-    sz = __builtin_fmaf(mult, q[2], sz);
+// row e's term of its point's geo sum
+__device__ __forceinline__ void geo_add_row(GeoSum &g, const TileMapView &tm, const float *__restrict__ new_xyz, int e) {
+    const unsigned info = tm.rowinfo[e];
+    g.add((float)((info >> 16) & 0xffu), new_xyz + (size_t)(tm.tq0[e >> 5] + (int)(info & 0xffu)) * 3);
 }
 
-__global__ __launch_bounds__(128) void csr_sort_short_kernel(int nq, long long npts, const int *__restrict__ tmap,
+__global__ __launch_bounds__(128) void csr_sort_short_kernel(int nq, int b, long long npts, const int *__restrict__ tmap,
                                                              const int *__restrict__ pcnt, int *__restrict__ poff,
                                                              int *__restrict__ plist,
                                                              const float *__restrict__ new_xyz,
@@ -653,24 +613,19 @@ __global__ __launch_bounds__(128) void csr_sort_short_kernel(int nq, long long n
     const int start = poff[gn] - c;
     poff[gn] = start;
     int *__restrict__ l = plist + start;
-    const unsigned *__restrict__ rows = reinterpret_cast<const unsigned *>(tmap + 4 + ((nq + 3) & ~3));
+    const TileMapView tm(tmap, nq, b);
     const int t = threadIdx.x;
-    for (int i = 0; i < c; ++i) {
-        const int v = l[i];
-        int j = i;
-        for (; j > 0 && slice[j - 1][t] > v; --j) slice[j][t] = slice[j - 1][t];
-        slice[j][t] = v;
-    }
-    float occ = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    list_insertion_sort<129>(l, &slice[0][t], 0, c);
+    GeoSum g;
     for (int i = 0; i < c; ++i) {
         const int e = slice[i][t];
         l[i] = e;
-        if (geo) geo_add(tmap, rows, new_xyz, e, occ, sx, sy, sz);
+        if (geo) geo_add_row(g, tm, new_xyz, e);
     }
-    if (geo) *reinterpret_cast<float4 *>(geo + gn * 4) = make_float4(occ, sx, sy, sz);
+    if (geo) g.store(geo + gn * 4);
 }
 
-__global__ __launch_bounds__(256) void csr_sort_long_kernel(int nq, long long npts, const int *__restrict__ tmap,
+__global__ __launch_bounds__(256) void csr_sort_long_kernel(int nq, int b, long long npts, const int *__restrict__ tmap,
                                                             const int *__restrict__ pcnt, int *__restrict__ poff,
                                                             int *__restrict__ plist,
                                                             const float *__restrict__ new_xyz,
@@ -683,29 +638,18 @@ __global__ __launch_bounds__(256) void csr_sort_long_kernel(int nq, long long np
     if (c <= CSR_SHORT) return;                             // csr_sort_short's
     const int start = poff[gn] - c;
     int *__restrict__ l = plist + start;
-    const unsigned *__restrict__ rows = reinterpret_cast<const unsigned *>(tmap + 4 + ((nq + 3) & ~3));
-    float occ = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    const TileMapView tm(tmap, nq, b);
+    GeoSum g;
     if (c <= CSR_LONG) {
         int n = 32;
         while (n < c) n <<= 1;
-        int *b = buf[w];
-        // (one wave owns b: its LDS operations execute in program order, no barrier between the stages)
-        for (int i = lane; i < n; i += 64) b[i] = i < c ? l[i] : 0x7fffffff;
-        for (int k = 2; k <= n; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < n / 2; t += 64) {
-                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));     // the lower index of pair t at distance j
-                    const int p = i | j;
-                    const bool up = (i & k) == 0;
-                    const int x = b[i], y = b[p];
-                    if ((x > y) == up) { b[i] = y; b[p] = x; }
-                }
-            }
-        }
+        int *s = buf[w];
+        for (int i = lane; i < n; i += 64) s[i] = i < c ? l[i] : 0x7fffffff;
+        wave_lds_bitonic_sort(s, n, lane);
         for (int i = lane; i < c; i += 64) {
-            const int e = b[i];
+            const int e = s[i];
             l[i] = e;
-            if (geo) geo_add(tmap, rows, new_xyz, e, occ, sx, sy, sz);
+            if (geo) geo_add_row(g, tm, new_xyz, e);
         }
     } else if (lane == 0) {
         for (int gap = 1093; gap > 0; gap = gap == 1 ? 0 : (gap - 1) / 3) {
@@ -717,20 +661,17 @@ __global__ __launch_bounds__(256) void csr_sort_long_kernel(int nq, long long np
             }
         }
         if (geo)
-            for (int i = 0; i < c; ++i) geo_add(tmap, rows, new_xyz, l[i], occ, sx, sy, sz);
+            for (int i = 0; i < c; ++i) geo_add_row(g, tm, new_xyz, l[i]);
     }
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) {
-        occ += __shfl_xor(occ, k); sx += __shfl_xor(sx, k); sy += __shfl_xor(sy, k); sz += __shfl_xor(sz, k);
-    }
+    g.wave_sum();                                           // (Shell's path: lane 0 holds the sum, the others add zeros)
     if (lane == 0) {
         poff[gn] = start;
-        if (geo) *reinterpret_cast<float4 *>(geo + gn * 4) = make_float4(occ, sx, sy, sz);
+        if (geo) g.store(geo + gn * 4);
     }
 }
 
 
-// The same inverse map by ONE launch, one workgroup per cloud, everything in LDS (round 4: the six launches above cost
+// The same inverse map by ONE launch, one workgroup per cloud, everything in LDS (the six launches above cost
 // 46-72 us per stage on the classifier's critical path for a few thousand rows per cloud).  A list entry travels as
 //   (row within the cloud) << 16 | mult << 10 | (query within the cloud)
 // so that sorting the words sorts the rows and geo needs nothing but the cloud's query coordinates (LDS too).
@@ -741,7 +682,7 @@ __global__ __launch_bounds__(256) void csr_sort_long_kernel(int nq, long long np
 // pure function of idx the kernels above compute; geo is summed in ascending row order (lists up to CSR_INS) or
 // lane-strided + butterfly (longer): fixed orders.  For m <= 1024 (query bits), rows <= 65536 and what fits in LDS.
 constexpr int CSR_INS = 16;      // lists up to here: insertion by the point's thread; up to 64: a wave's bitonic network in registers
-// Round 5: optional `rowdst` = the INVERSE of plist (rowdst[row] = the row's place in the point-sorted order): the
+// Optional `rowdst` = the INVERSE of plist (rowdst[row] = the row's place in the point-sorted order): the
 // register-resident backward pass stores a row's g_u at that place, so that a point's rows are CONTIGUOUS and its consumer
 // sums them in a fixed order without a list (csrc/sa_fused.hip, sa_glue.hip).  blockIdx.y = batch z of a stacked index
 // stage: map z at tmap + z * tmap_stride ints, every other array at its own per-batch stride (plist may be null then).
@@ -773,11 +714,10 @@ __global__ __launch_bounds__(1024) void csr_cloud_kernel(int nq, int b, int n, i
     int *slong = reinterpret_cast<int *>(sq + 3 * m);                    // points with long lists (at most rows_cap / CSR_INS)
     int *sbit = slong + rows_cap / CSR_INS + 1;                          // [16 waves][bitonic_words]: a long list, padded to a power of two
     const int cloud = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int *__restrict__ tq0 = tmap + 4;
-    const unsigned *__restrict__ rows = reinterpret_cast<const unsigned *>(tmap + 4 + ((nq + 3) & ~3));
-    const int *__restrict__ rownn = reinterpret_cast<const int *>(rows + (size_t)32 * nq);
-    const int *__restrict__ tcount = rownn + (size_t)32 * nq, *__restrict__ toff = tcount + b;
-    const int row0 = toff[cloud] * 32, nrows = tcount[cloud] * 32;
+    const TileMapView tm(tmap, nq, b);
+    const int *__restrict__ tq0 = tm.tq0, *__restrict__ rownn = tm.rownn;
+    const unsigned *__restrict__ rows = tm.rowinfo;
+    const int row0 = tm.toff[cloud] * 32, nrows = tm.tcount[cloud] * 32;
     const size_t cbase = (size_t)cloud * n;
     const int qbase = cloud * m;
     for (int k = t; k < n; k += 1024) { scnt[k] = 0; if (fq) fq[cbase + k] = -1; }
@@ -799,10 +739,10 @@ __global__ __launch_bounds__(1024) void csr_cloud_kernel(int nq, int b, int n, i
         }
         if (twice) sdup = 1;
     }
-    // count (and which query each sampled point is: one row per query has slot 0).  Round 5: a thread's rows are requested
-    // in batches of eight -- record, neighbour and first query of the tile, clamped, unconditional -- and, when the cloud has
+    // count (and which query each sampled point is: one row per query has slot 0).  A thread's rows are requested in
+    // batches of eight -- record, neighbour and first query of the tile, clamped, unconditional -- and, when the cloud has
     // at most 8192 rows (always at stage 1), KEPT for the fill pass: a loop of one dependent round trip per row (4-5 per thread
-    // and pass at stage 1) was most of this kernel's 16 us
+    // and pass at stage 1) is most of a 16 us kernel
     constexpr int RB = 8;
     unsigned k_info[RB];
     int k_nn[RB], k_q0[RB];
@@ -841,32 +781,9 @@ __global__ __launch_bounds__(1024) void csr_cloud_kernel(int nq, int b, int n, i
         if (k < n) sum += scnt[k];
     }
     {
-        // inclusive scan over the 1024 threads: inside a wave by lane exchanges, the sixteen wave totals by wave 0 -- two
-        // barriers (round 5; the Hillis-Steele form over LDS took twenty, ~5 of the kernel's 16 us)
-        int incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
-        __shared__ int wtot[16];
-        if (lane == 63) wtot[wave] = incl;
+        int run = block_exclusive_scan_1024(sum);
+        part[t] = run + sum;                            // (part[1023], the cloud's total, is read by every thread at the end)
         __syncthreads();
-        if (wave == 0) {
-            int w = lane < 16 ? wtot[lane] : 0;
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) {
-                const int v = __shfl_up(w, d);
-                if (lane >= d) w += v;
-            }
-            if (lane < 16) wtot[lane] = w;
-        }
-        __syncthreads();
-        part[t] = incl + (wave > 0 ? wtot[wave - 1] : 0);
-    }
-    __syncthreads();                                    // (part[1023], the cloud's total, is read by every thread at the end)
-    {
-        int run = part[t] - sum;
         for (int i = 0; i < per; ++i) {
             const int k = t * per + i;
             if (k < n) {
@@ -895,33 +812,26 @@ __global__ __launch_bounds__(1024) void csr_cloud_kernel(int nq, int b, int n, i
         }
     }
     __syncthreads();
-    auto geo_term = [&](int w, float &occ, float &sx, float &sy, float &sz) {
-        const float mult = (float)((w >> 10) & 63);
-        const float *__restrict__ q = sq + 3 * (w & 1023);
-        occ += mult;
-        sx = __builtin_fmaf(mult, q[0], sx);
-        sy = __builtin_fmaf(mult, q[1], sy);
-        sz = __builtin_fmaf(mult, q[2], sz);
-    };
+    auto geo_add_word = [&](GeoSum &g, int w) { g.add((float)((w >> 10) & 63), sq + 3 * (w & 1023)); };
     // short lists: the point's thread
     for (int k = t; k < n; k += 1024) {
         const int start = soff[k], c = scnt[k] - start;
         if (c > CSR_INS) continue;
         int *l = slist + start;
-        for (int i = 1; i < c; ++i) {
-            const int v = l[i];
-            int j = i;
-            for (; j > 0 && l[j - 1] > v; --j) l[j] = l[j - 1];
-            l[j] = v;
-        }
-        float occ = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        for (int i = 0; i < c; ++i) geo_term(l[i], occ, sx, sy, sz);
-        if (geo) *reinterpret_cast<float4 *>(geo + (cbase + k) * 4) = make_float4(occ, sx, sy, sz);
+        list_insertion_sort<1>(l, l, 1, c);
+        GeoSum g;
+        for (int i = 0; i < c; ++i) geo_add_word(g, l[i]);
+        if (geo) g.store(geo + (cbase + k) * 4);
     }
-    // longer lists: a wave each
+    // longer lists: a wave each (lane-strided terms, then the butterfly)
+    auto put_wave_geo = [&](GeoSum &g, int k) {
+        g.wave_sum();
+        if (lane == 0 && geo) g.store(geo + (cbase + k) * 4);
+    };
     for (int li = wave; li < nlong; li += 16) {
         const int k = slong[li], start = soff[k], c = scnt[k] - start;
         int *l = slist + start;
+        GeoSum g;
         if (c <= 64) {                                          // (wave-uniform) one entry per lane, bitonic over the lanes
             int v = lane < c ? l[lane] : 0x7fffffff;
 #pragma unroll
@@ -934,45 +844,25 @@ __global__ __launch_bounds__(1024) void csr_cloud_kernel(int nq, int b, int n, i
                 }
             }
             if (lane < c) l[lane] = v;
-            float occ = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
-            if (lane < c) geo_term(v, occ, sx, sy, sz);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                occ += __shfl_xor(occ, o); sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o);
-            }
-            if (lane == 0 && geo) *reinterpret_cast<float4 *>(geo + (cbase + k) * 4) = make_float4(occ, sx, sy, sz);
+            if (lane < c) geo_add_word(g, v);
+            put_wave_geo(g, k);
             continue;
         }
         if (c <= bitonic_words) {
             // a bitonic network over this wave's LDS buffer (a thread's insertion sort is a chain of dependent LDS
             // operations, the rank form below is quadratic: 17 us for a list of 256 -- collapsed clouds have 32 such
-            // lists per cloud)  (one wave owns the buffer: its LDS operations execute in program order)
+            // lists per cloud)
             int nn2 = 128;
             while (nn2 < c) nn2 <<= 1;
             int *bb = sbit + wave * bitonic_words;
             for (int i = lane; i < nn2; i += 64) bb[i] = i < c ? l[i] : 0x7fffffff;
-            for (int kk = 2; kk <= nn2; kk <<= 1) {
-                for (int j = kk >> 1; j > 0; j >>= 1) {
-                    for (int t2 = lane; t2 < nn2 / 2; t2 += 64) {
-                        const int i = ((t2 & ~(j - 1)) << 1) | (t2 & (j - 1));       // the lower index of pair t2 at distance j
-                        const int pp = i | j;
-                        const bool up = (i & kk) == 0;
-                        const int x = bb[i], y = bb[pp];
-                        if ((x > y) == up) { bb[i] = y; bb[pp] = x; }
-                    }
-                }
-            }
-            float occ = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+            wave_lds_bitonic_sort(bb, nn2, lane);
             for (int i = lane; i < c; i += 64) {
                 const int e2 = bb[i];
                 l[i] = e2;
-                geo_term(e2, occ, sx, sy, sz);
+                geo_add_word(g, e2);
             }
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                occ += __shfl_xor(occ, o); sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o);
-            }
-            if (lane == 0 && geo) *reinterpret_cast<float4 *>(geo + (cbase + k) * 4) = make_float4(occ, sx, sy, sz);
+            put_wave_geo(g, k);
             continue;
         }
         // ranks first, all of them, then the moves (one wave's LDS operations execute in order)
@@ -994,13 +884,8 @@ __global__ __launch_bounds__(1024) void csr_cloud_kernel(int nq, int b, int n, i
 #pragma unroll
         for (int u = 0; u < 16; ++u)
             if (lane + 64 * u < cc) l[rank[u]] = mine[u];
-        float occ = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        for (int i = lane; i < cc; i += 64) geo_term(l[i], occ, sx, sy, sz);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            occ += __shfl_xor(occ, o); sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o);
-        }
-        if (lane == 0 && geo) *reinterpret_cast<float4 *>(geo + (cbase + k) * 4) = make_float4(occ, sx, sy, sz);
+        for (int i = lane; i < cc; i += 64) geo_add_word(g, l[i]);
+        put_wave_geo(g, k);
     }
     __syncthreads();
     const int total = part[1023];
@@ -1020,19 +905,17 @@ __global__ __launch_bounds__(256) void rowdst_kernel(long long npts, const int *
     for (int i = 0; i < c; ++i) rowdst[plist[s0 + i]] = s0 + i;
 }
 
+// the row map's per-cloud verdict where the picks are not examined: 1
+__global__ __launch_bounds__(256) void rowmap_dup_unknown_kernel(int b, int *__restrict__ dup) {
+    for (int k = threadIdx.x; k < b; k += 256) dup[k] = 1;
+}
+
 }  // namespace apn
 
-// The map is ONE int32 blob (BM = b * m, BM4 = BM rounded up to 4):
-//   [0] tiles in use   [4, 4 + BM) tq0   [4 + BM4, + 32 BM) rowinfo   [.., + 32 BM) rownn = each row's neighbour
-//   (idx[query][slot], so that the passes need no second dependent load)   then scratch of this builder
-// (per-cloud tile counts and offsets, per-query packing records); apn_sa_wide_tilemap_ints(b, m) = its size.
-static size_t tilemap_rows_off(int bm) { return 4 + (size_t)((bm + 3) & ~3); }
-
+// The map is ONE int32 blob, laid out by csrc/tile_map.h; apn_sa_wide_tilemap_ints(b, m) = its size.
 extern "C" int apn_sa_wide_tilemap_ints(int b, int m) {
     if (b <= 0 || m <= 0 || (long long)b * m > 0x7fffffffLL / 64) return 0;
-    const size_t bm = (size_t)b * m;
-    // (a multiple of four ints: maps stacked back to back by apn_sa_wide_tilemap_many stay 16-byte aligned)
-    return (int)((tilemap_rows_off((int)bm) + 64 * bm + 2 * (size_t)b + bm + (bm + 1) / 2 + (bm + 3) / 4 + 8 + 3) & ~(size_t)3);
+    return (int)apn::tile_map_ints(b * m, b);
 }
 
 // count maps in one pair of launches: map z reads idx + z * b * m * 32 and fills tmap + z * tilemap_ints(b, m)
@@ -1044,12 +927,12 @@ extern "C" int apn_sa_wide_tilemap_many(int count, int b, int m, int mode, const
     const int nq = b * m;
     const long long idx_stride = (long long)nq * 32, blob_bytes = (long long)apn_sa_wide_tilemap_ints(b, m) * 4;
     int *tq0 = tmap + 4;
-    unsigned *rowinfo = (unsigned *)(tmap + tilemap_rows_off(nq));
-    int *rownn = (int *)(rowinfo + (size_t)32 * nq);
-    int *tcount = rownn + (size_t)32 * nq, *toff = tcount + b;
-    unsigned *qmeta = (unsigned *)(toff + b);
-    unsigned short *tnq_local = (unsigned short *)(qmeta + nq);
-    unsigned char *cnt8 = (unsigned char *)(tnq_local + 2 * (((size_t)nq + 1) / 2));
+    unsigned *rowinfo = (unsigned *)(tmap + apn::tile_map_rowinfo_off(nq));
+    int *rownn = tmap + apn::tile_map_rownn_off(nq);
+    int *tcount = tmap + apn::tile_map_tcount_off(nq), *toff = tmap + apn::tile_map_toff_off(nq, b);
+    unsigned *qmeta = (unsigned *)(tmap + apn::tile_map_qmeta_off(nq, b));
+    unsigned short *tnq_local = (unsigned short *)(tmap + apn::tile_map_tnq_local_off(nq, b));
+    unsigned char *cnt8 = (unsigned char *)(tmap + apn::tile_map_cnt8_off(nq, b));
     hipStream_t st = (hipStream_t)stream;
     if (m <= 2048) {
         int levels = 1;
@@ -1079,6 +962,54 @@ extern "C" int apn_sa_wide_tilemap(int b, int m, int mode, const int *idx, int *
     return apn_sa_wide_tilemap_many(1, b, m, mode, idx, tmap, stream);
 }
 
+// The reverse lists of `count` stacked tile maps (map z at tmap + z * apn_sa_wide_tilemap_ints(b, m), every other array at
+// its own per-batch stride, as in csr_cloud_kernel), behind apn_sa_wide_csr and apn_sa_rowmap_many.  With rowdst: the row
+// map's form -- a batch's blob is pcnt | poff | per-cloud pick verdict, plist may be null.  One launch, one workgroup
+// per cloud, when a cloud's map fits in LDS; otherwise six launches per batch over `list` (plist, or the caller's scratch).
+static int reverse_lists(int count, int b, int n, int m, const int *tmap, const float *new_xyz, int *pcnt_poff, int *plist,
+                         float *geo, const int *fidx, int *fq, int *rowdst, int *scratch, hipStream_t st) {
+    const int nq = b * m;
+    const long long npts = (long long)b * n, tstride = apn_sa_wide_tilemap_ints(b, m), blob = 2 * npts + (rowdst ? b : 0);
+    const long long rows_cap = (long long)m * 32;
+    long long lds = 4 * (2ll * n + rows_cap + 3ll * m + rows_cap / apn::CSR_INS + 1);
+    int bitonic_words = 0;                                   // per wave: a buffer for lists of up to this many rows
+    for (int wds = 1024; wds >= 128; wds >>= 1)
+        if (lds + 16ll * wds * 4 <= 150 * 1024) { bitonic_words = wds; break; }
+    if (m <= 1024 && rows_cap <= 65536 && lds <= 150 * 1024) {
+        lds += 16ll * bitonic_words * 4;
+        static apn::DynLdsOnce configured;       // (per device: apn_common.h)
+        if (hipError_t e = apn::set_dyn_lds(configured, (const void *)apn::csr_cloud_kernel, 150 * 1024)) return (int)e;
+        hipLaunchKernelGGL(apn::csr_cloud_kernel, dim3(b, count), dim3(1024), (size_t)lds, st, nq, b, n, m, tmap, new_xyz,
+                           pcnt_poff, pcnt_poff + npts, plist, geo, fidx, fq, (int)rows_cap, bitonic_words, rowdst, tstride,
+                           rowdst ? pcnt_poff : (int *)nullptr);
+        APN_LAUNCH_CHECK();
+        return APN_OK;
+    }
+    const unsigned rb = (unsigned)(((long long)nq * 32 + 255) / 256), pb = (unsigned)((npts + 255) / 256);
+    for (long long z = 0; z < count; ++z) {
+        const int *tm = tmap + z * tstride;
+        int *pcnt = pcnt_poff + z * blob, *poff = pcnt + npts, *list = plist ? plist + z * 32 * nq : scratch;
+        const float *q = new_xyz ? new_xyz + z * 3 * nq : nullptr;
+        float *g = geo ? geo + z * 4 * npts : nullptr;
+        const int *fi = fidx ? fidx + z * nq : nullptr;
+        int *fqz = fq ? fq + z * npts : nullptr;
+        if (rowdst)                                          // (the picks are not examined on this path)
+            hipLaunchKernelGGL(apn::rowmap_dup_unknown_kernel, dim3(1), dim3(256), 0, st, b, pcnt + 2 * npts);
+        hipLaunchKernelGGL(apn::csr_init_kernel, dim3(pb), dim3(256), 0, st, npts, pcnt, fqz);
+        hipLaunchKernelGGL(apn::csr_count_fill_kernel, dim3(rb), dim3(256), 0, st, nq, b, n, m, 0, tm, pcnt, poff, list, fi, fqz);
+        hipLaunchKernelGGL(apn::csr_scan_kernel, dim3(b), dim3(1024), 0, st, n, tm + apn::tile_map_toff_off(nq, b), 0, pcnt,
+                           poff, (int *)nullptr);
+        hipLaunchKernelGGL(apn::csr_count_fill_kernel, dim3(rb), dim3(256), 0, st, nq, b, n, m, 1, tm, pcnt, poff, list, fi, fqz);
+        hipLaunchKernelGGL(apn::csr_sort_short_kernel, dim3((unsigned)((npts + 127) / 128)), dim3(128), 0, st, nq, b, npts, tm,
+                           pcnt, poff, list, q, g);
+        hipLaunchKernelGGL(apn::csr_sort_long_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, st, nq, b, npts, tm,
+                           pcnt, poff, list, q, g);
+        if (rowdst) hipLaunchKernelGGL(apn::rowdst_kernel, dim3(pb), dim3(256), 0, st, npts, pcnt, poff, list, rowdst + z * 32 * nq);
+    }
+    APN_LAUNCH_CHECK();
+    return APN_OK;
+}
+
 // pcnt_poff: int32[2 b n] (counts, then list starts); plist: int32[32 b m]; geo: float[4 b n] (optional);
 // optional: fidx (b,m) = the point every query is -> fq int32[b n] = the query a point is, or -1.
 extern "C" int apn_sa_wide_csr(int b, int n, int m, const int *idx, const float *new_xyz, const int *tmap,
@@ -1087,54 +1018,22 @@ extern "C" int apn_sa_wide_csr(int b, int n, int m, const int *idx, const float 
         (long long)b * n > 0x7fffffffLL / 8 || !idx || !new_xyz || !tmap || !pcnt_poff || !plist ||
         ((fidx != nullptr) != (fq != nullptr)))
         return APN_EINVAL;
-    const int nq = b * m;
-    const long long npts = (long long)b * n;
-    int *pcnt = pcnt_poff, *poff = pcnt_poff + npts;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        // one launch, one workgroup per cloud, when a cloud's map fits in LDS
-        const long long rows_cap = (long long)m * 32;
-        long long lds = 4 * (2ll * n + rows_cap + 3ll * m + rows_cap / apn::CSR_INS + 1);
-        int bitonic_words = 0;                                   // per wave: a buffer for lists of up to this many rows
-        for (int wds = 1024; wds >= 128; wds >>= 1)
-            if (lds + 16ll * wds * 4 <= 150 * 1024) { bitonic_words = wds; break; }
-        if (m <= 1024 && rows_cap <= 65536 && lds <= 150 * 1024) {
-            lds += 16ll * bitonic_words * 4;
-            static apn::DynLdsOnce configured;       // (per device: apn_common.h)
-            if (hipError_t e = apn::set_dyn_lds(configured, (const void *)apn::csr_cloud_kernel, 150 * 1024)) return (int)e;
-            hipLaunchKernelGGL(apn::csr_cloud_kernel, dim3(b), dim3(1024), (size_t)lds, st, nq, b, n, m, tmap, new_xyz, pcnt,
-                               poff, plist, geo, fidx, fq, (int)rows_cap, bitonic_words, (int *)nullptr, 0ll, (int *)nullptr);
-            APN_LAUNCH_CHECK();
-            return APN_OK;
-        }
-    }
-    hipLaunchKernelGGL(apn::csr_init_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, npts, pcnt, fq);
-    const unsigned rb = (unsigned)(((long long)nq * 32 + 255) / 256);
-    hipLaunchKernelGGL(apn::csr_count_fill_kernel, dim3(rb), dim3(256), 0, st, nq, n, m, 0, idx, tmap, pcnt, poff, plist,
-                       fidx, fq);
-    hipLaunchKernelGGL(apn::csr_scan_kernel, dim3(b), dim3(1024), 0, st, nq, b, n, tmap, pcnt, poff);
-    hipLaunchKernelGGL(apn::csr_count_fill_kernel, dim3(rb), dim3(256), 0, st, nq, n, m, 1, idx, tmap, pcnt, poff, plist,
-                       fidx, fq);
-    hipLaunchKernelGGL(apn::csr_sort_short_kernel, dim3((unsigned)((npts + 127) / 128)), dim3(128), 0, st, nq, npts, tmap,
-                       pcnt, poff, plist, new_xyz, geo);
-    hipLaunchKernelGGL(apn::csr_sort_long_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, st, nq, npts, tmap,
-                       pcnt, poff, plist, new_xyz, geo);
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return reverse_lists(1, b, n, m, tmap, new_xyz, pcnt_poff, plist, geo, fidx, fq, nullptr, nullptr, (hipStream_t)stream);
 }
 
-// The ROW MAP of the register-resident backward pass (round 5), `count` stacked batches in one launch: per batch z
-//   pcnt_poff + z * 2 b n   int32[2 b n]: per support point the number of tile-map rows that gather it, and the first place
-//                           of its rows in the point-sorted order (places share the row ids' index space: a cloud's places
-//                           lie inside the cloud's own range of row ids);
+// The ROW MAP of the register-resident backward pass, `count` stacked batches in one launch: per batch z
+//   pcnt_poff + z * (2 b n + b)   int32[2 b n]: per support point the number of tile-map rows that gather it, and the first
+//                           place of its rows in the point-sorted order (places share the row ids' index space: a cloud's
+//                           places lie inside the cloud's own range of row ids); then int32[b]: the per-cloud verdict on the
+//                           picks (csr_cloud_kernel's dup);
 //   rowdst + z * 32 b m     int32[32 b m]: the place of every live row of map z (tmap + z * apn_sa_wide_tilemap_ints(b, m)): the
 //                           row of GU (apn_sa_rowmap_places(b, n, m) rows) its g_u is stored in.  A point's rows occupy
-//                           consecutive places in ascending row order.  (Measured and removed in round 5: the first ELL = 8
-//                           rows of a point at a MAP-FREE address point * ELL + j, requested together with the count -- one
-//                           round trip instead of two dependent ones, but 64 KB instead of 31 KB per 64-point tile and fully
-//                           scattered stores: the per-point kernel 15.3 -> 17.1 us.)
-// The map is a pure function of the neighbour indices (index-stage data, like the tile map).  scratch: int32[32 b m], used by the multi-launch path only (clouds whose map does not
-// fit one workgroup's LDS).
+//                           consecutive places in ascending row order.  (Measured and rejected: the first ELL = 8 rows of a
+//                           point at a MAP-FREE address point * ELL + j, requested together with the count -- one round trip
+//                           instead of two dependent ones, but 64 KB instead of 31 KB per 64-point tile and fully scattered
+//                           stores: the per-point kernel 15.3 -> 17.1 us.)
+// The map is a pure function of the neighbour indices (index-stage data, like the tile map).  scratch: int32[32 b m], used
+// by the multi-launch path only (clouds whose map does not fit one workgroup's LDS).
 // rows of GU a backward needs: one per tile-map row
 extern "C" int apn_sa_rowmap_places(int b, int n, int m) {
     const long long rows = 32ll * b * m;
@@ -1146,53 +1045,12 @@ extern "C" int apn_sa_rowmap_ints(int b, int n) {
     return (b <= 0 || n <= 0 || v > 0x7fffffffLL) ? 0 : (int)v;
 }
 
-namespace apn {
-__global__ __launch_bounds__(256) void rowmap_dup_unknown_kernel(int b, int *__restrict__ dup) {
-    for (int k = threadIdx.x; k < b; k += 256) dup[k] = 1;
-}
-}  // namespace apn
-
 extern "C" int apn_sa_rowmap_many(int count, int b, int n, int m, const int *tmap, const int *fidx, int *pcnt_poff, int *rowdst,
                                   int *scratch, void *stream) {
     if (32ll * b * m > 0x7fffffffLL / 128) return APN_EINVAL;     // places as 32-bit byte offsets / 128
     if (count <= 0 || count > 65535 || b <= 0 || n <= 0 || m <= 0 || b > 65535 || (long long)b * m > 0x7fffffffLL / 64 ||
         (long long)b * n > 0x7fffffffLL / 8 || !tmap || !pcnt_poff || !rowdst || !scratch)
         return APN_EINVAL;
-    const int nq = b * m;
-    const long long npts = (long long)b * n, tstride = apn_sa_wide_tilemap_ints(b, m);
-    hipStream_t st = (hipStream_t)stream;
-    const long long rows_cap = (long long)m * 32;
-    long long lds = 4 * (2ll * n + rows_cap + 3ll * m + rows_cap / apn::CSR_INS + 1);
-    int bitonic_words = 0;
-    for (int wds = 1024; wds >= 128; wds >>= 1)
-        if (lds + 16ll * wds * 4 <= 150 * 1024) { bitonic_words = wds; break; }
-    if (m <= 1024 && rows_cap <= 65536 && lds <= 150 * 1024) {
-        lds += 16ll * bitonic_words * 4;
-        static apn::DynLdsOnce configured;
-        if (hipError_t e = apn::set_dyn_lds(configured, (const void *)apn::csr_cloud_kernel, 150 * 1024)) return (int)e;
-        hipLaunchKernelGGL(apn::csr_cloud_kernel, dim3(b, count), dim3(1024), (size_t)lds, st, nq, b, n, m, tmap,
-                           (const float *)nullptr, pcnt_poff, pcnt_poff + npts, (int *)nullptr, (float *)nullptr,
-                           fidx, (int *)nullptr, (int)rows_cap, bitonic_words, rowdst, tstride, pcnt_poff);
-        APN_LAUNCH_CHECK();
-        return APN_OK;
-    }
-    const unsigned rb = (unsigned)(((long long)nq * 32 + 255) / 256);
-    for (int z = 0; z < count; ++z) {
-        const int *tm = tmap + z * tstride;
-        int *pcnt = pcnt_poff + z * (2 * npts + b), *poff = pcnt + npts, *rd = rowdst + (long long)z * 32 * nq;
-        hipLaunchKernelGGL(apn::rowmap_dup_unknown_kernel, dim3(1), dim3(256), 0, st, b, pcnt + 2 * npts);   // (picks not examined on this path)
-        hipLaunchKernelGGL(apn::csr_init_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, npts, pcnt, (int *)nullptr);
-        hipLaunchKernelGGL(apn::csr_count_fill_kernel, dim3(rb), dim3(256), 0, st, nq, n, m, 0, (const int *)nullptr, tm, pcnt, poff,
-                           scratch, (const int *)nullptr, (int *)nullptr);
-        hipLaunchKernelGGL(apn::csr_scan_kernel, dim3(b), dim3(1024), 0, st, nq, b, n, tm, pcnt, poff);
-        hipLaunchKernelGGL(apn::csr_count_fill_kernel, dim3(rb), dim3(256), 0, st, nq, n, m, 1, (const int *)nullptr, tm, pcnt, poff,
-                           scratch, (const int *)nullptr, (int *)nullptr);
-        hipLaunchKernelGGL(apn::csr_sort_short_kernel, dim3((unsigned)((npts + 127) / 128)), dim3(128), 0, st, nq, npts, tm, pcnt,
-                           poff, scratch, (const float *)nullptr, (float *)nullptr);
-        hipLaunchKernelGGL(apn::csr_sort_long_kernel, dim3((unsigned)((npts + 3) / 4)), dim3(256), 0, st, nq, npts, tm, pcnt,
-                           poff, scratch, (const float *)nullptr, (float *)nullptr);
-        hipLaunchKernelGGL(apn::rowdst_kernel, dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st, npts, pcnt, poff, scratch, rd);
-    }
-    APN_LAUNCH_CHECK();
-    return APN_OK;
+    return reverse_lists(count, b, n, m, tmap, nullptr, pcnt_poff, nullptr, nullptr, fidx, nullptr, rowdst, scratch,
+                         (hipStream_t)stream);
 }

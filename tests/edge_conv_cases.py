@@ -57,7 +57,7 @@ SLOPES = (0.0, 0.25)
 RESIDUALS = ("none", "contiguous", "permuted", "expanded")
 G_LAYOUTS = ("contiguous", "permuted", "scalar")
 LADDER = (0, 1, 2, 3, 5, 63, 64, 65, 127, 128, 129)
-CSR_ONLY = ((2, 1025, 3), (1, 2049, 2), (3, 1024, 1))    # ec_csr_scan_kernel's `per` = 2, 3, 1
+CSR_ONLY = ((2, 1025, 3), (1, 2049, 2), (3, 1024, 1))    # csr_scan_kernel's `per` = 2, 3, 1
 
 Case = collections.namedtuple("Case", "name seed B N H K kind ld_pad gamma slope res g")
 

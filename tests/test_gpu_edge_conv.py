@@ -139,6 +139,15 @@ def test_arbitrary_indices(dev):
              make_idx=lambda x: torch.zeros(x.shape[0], x.shape[2], 20, dtype=torch.int32, device=x.device))
 
 
+def _assert_lists_of(tgt, rows, pcnt_poff, plist):
+    """pcnt / poff / plist are the reverse lists of the positions whose targets (flat rows) are tgt: a stable argsort."""
+    pcnt, poff = pcnt_poff.cpu().numpy()
+    order = np.argsort(tgt, kind="stable")                           # positions by the point they gather, ascending
+    assert np.array_equal(pcnt, np.bincount(tgt, minlength=rows))
+    assert np.array_equal(poff, np.cumsum(pcnt) - pcnt)
+    assert np.array_equal(plist.cpu().numpy(), order.astype(np.int32))
+
+
 def test_reverse_lists_are_the_positions_in_ascending_order(dev):
     """apn_ec_csr against numpy, for a kNN graph, for repeated / missing neighbours and for idx = 0."""
     from adaptpoint_amd.edge_conv import edge_index
@@ -146,15 +155,27 @@ def test_reverse_lists_are_the_positions_in_ascending_order(dev):
     for idx in (_knn(x, 20), _random_half(x), torch.zeros(3, 150, 33, dtype=torch.int32, device=dev)):
         B, N, K = idx.shape
         g = edge_index(idx)
-        pcnt, poff = g.pcnt_poff.cpu().numpy()
-        plist = g.plist.cpu().numpy()
         tgt = (idx.cpu().numpy().astype(np.int64) + (np.arange(B) * N)[:, None, None]).reshape(-1)
-        order = np.argsort(tgt, kind="stable")                       # positions by the point they gather, ascending
-        assert np.array_equal(pcnt, np.bincount(tgt, minlength=B * N))
-        assert np.array_equal(poff, np.cumsum(pcnt) - pcnt)
-        assert np.array_equal(plist, order.astype(np.int32))
+        _assert_lists_of(tgt, B * N, g.pcnt_poff, g.plist)
         again = edge_index(idx)
         assert torch.equal(again.plist, g.plist) and torch.equal(again.pcnt_poff, g.pcnt_poff)
+
+
+def test_reverse_lists_where_the_scan_takes_several_points_per_thread(dev):
+    """The scan kernel shared by apn_ec_csr and apn_po_csr (csrc/reverse_lists.h) is one workgroup of 1024 threads per
+    cloud: clouds of 1025 points (two per thread, two clouds: the second one's base) and one set of 2049 rows (three per
+    thread) gathered by 700 x 3 positions, against the same numpy statement."""
+    from adaptpoint_amd.edge_conv import edge_index
+    from adaptpoint_amd.pointops import build_csr
+    B, N, K = 2, 1025, 3
+    idx = torch.randint(0, N, (B, N, K), generator=torch.Generator().manual_seed(N), dtype=torch.int32)
+    g = edge_index(idx.to(dev))
+    tgt = (idx.numpy().astype(np.int64) + (np.arange(B) * N)[:, None, None]).reshape(-1)
+    _assert_lists_of(tgt, B * N, g.pcnt_poff, g.plist)
+    n, m, k = 2049, 700, 3
+    idx = torch.randint(0, n, (m, k), generator=torch.Generator().manual_seed(n), dtype=torch.int32)
+    c = build_csr(idx.to(dev), n)
+    _assert_lists_of(idx.numpy().astype(np.int64).reshape(-1), n, c.pcnt_poff, c.plist)
 
 
 def test_backward_is_bit_identical_from_run_to_run(dev):

@@ -274,7 +274,7 @@ def test_exact_cases_through_the_chain(dev, case):
 
 @pytest.mark.parametrize("shape", C.CSR_ONLY, ids=lambda s: "x".join(map(str, s)))
 def test_reverse_lists_of_clouds_above_1024_points(dev, shape):
-    """ec_csr_scan_kernel with 2, 3 and 1 points per thread; indices outside the cloud among them."""
+    """csr_scan_kernel with 2, 3 and 1 points per thread; indices outside the cloud among them."""
     B, N, K = shape
     idx = C.outside_graph(B, N, K, torch.Generator().manual_seed(N))
     got = ec_csr(dev, _in_int(dev, idx))

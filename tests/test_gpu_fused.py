@@ -655,17 +655,30 @@ def test_non_finite_upstream_gradient_is_loud(dev):
     assert torch.isnan(f.grad).any()
 
 
-@pytest.mark.parametrize("structure", ["ball", "random"])
-def test_row_map_is_the_point_sorted_order_of_the_tile_map_rows(dev, structure):
+def _random_rows(dev, B, N, M, seed=3):
+    """Arbitrary neighbour rows, some of them with the ball query's fill structure (the hits, then the first hit repeated)."""
+    idx = torch.randint(0, N, (B, M, 32), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
+    idx[:, ::3, 5:] = idx[:, ::3, :1]                # some rows with the fill structure, some with repeats that are not
+    idx[:, 1::7, 1:] = idx[:, 1::7, :1]              # and single-hit rows
+    return idx.to(dev)
+
+
+# (2, 1100, 1025): more than 1024 queries per cloud -- the multi-launch builder, which does not examine the picks
+@pytest.mark.parametrize("structure,B,N,M", [("ball", 6, 1024, 512), ("random", 6, 1024, 512), ("random", 2, 1100, 1025)],
+                         ids=["ball", "random", "random-2-1100-1025"])
+def test_row_map_is_the_point_sorted_order_of_the_tile_map_rows(dev, structure, B, N, M):
     """fused_wide.row_map (csrc/sa_wide_glue.hip: apn_sa_rowmap_many), index-stage data of the backward pass: every live
     row of the tile map has a place; the places of a cloud's rows fill a prefix of the cloud's own range of row ids; a
     point's rows hold consecutive places, in ascending row order; pcnt / poff say how many and where.  Against numpy, for
-    ball-query rows and for arbitrary ones; stacked maps (`row_maps`) equal the maps one by one."""
+    ball-query rows and for arbitrary ones, on the one-launch and on the multi-launch path; stacked maps (`row_maps`)
+    equal the maps one by one."""
     from adaptpoint_amd import _lib, fused_wide
-    B, N, M = 6, 1024, 512
-    p, new_p, f, idx, *_ = _setup(dev, B=B, seed=21)
-    if structure == "random":
+    if structure == "ball":
+        p, new_p, f, idx, *_ = _setup(dev, B=B, seed=21)
+    elif M == 512:
         idx = torch.randint(0, N, (B, M, 32), generator=torch.Generator().manual_seed(3), dtype=torch.int32).to(dev)
+    else:
+        idx = _random_rows(dev, B, N, M)
     tmap = fused_wide.tile_map(idx)
     pcnt_poff, rowdst = fused_wide.row_map(tmap, B, N, M)
     torch.cuda.synchronize()
@@ -715,6 +728,91 @@ def test_row_map_is_the_point_sorted_order_of_the_tile_map_rows(dev, structure):
         tz = maps[z].cpu().numpy()
         lz = ((tz[off:off + 32 * BM].view(np.uint32)[:32 * t_z] >> 16) & 0xff) != 0
         assert np.array_equal(rr[z].cpu().numpy()[:32 * t_z][lz], b_.cpu().numpy()[:32 * t_z][lz])
+
+
+# One workgroup's LDS holds a cloud's lists when 2 n + 37 m + 1 <= 38400 words (csrc/sa_wide_glue.hip: reverse_lists) and
+# m <= 1024: with m = 64 the last n that fits is 18015.  (2, 300, 97) fits; (2, 1100, 1025) does not, by its m.
+LIST_SHAPES = [(2, 300, 97), (2, 1100, 1025), (1, 18015, 64), (1, 18016, 64)]
+_LISTS = {}
+
+
+def _lists(dev, B, N, M):
+    """Both entries of the one reverse-list builder on one tile map of arbitrary rows -- fused_wide.neighbour_index
+    (apn_sa_wide_csr) and fused_wide.row_map (apn_sa_rowmap_many), the picks handed to both -- and the numpy statement of
+    what they hold, computed once per shape."""
+    if (B, N, M) in _LISTS:
+        return _LISTS[B, N, M]
+    from adaptpoint_amd import fused_wide
+    idx = _random_rows(dev, B, N, M, seed=N)
+    g = torch.Generator().manual_seed(M)
+    picks = torch.stack([torch.randperm(N, generator=g)[:M] for _ in range(B)]).int()          # distinct in every cloud
+    new_p = torch.rand(B, M, 3, generator=g)
+    nbr = fused_wide.neighbour_index(idx, new_p.to(dev), N, fidx=picks.to(dev))
+    pcnt_poff, rowdst = fused_wide.row_map(nbr.tmap, B, N, M, fidx=picks.to(dev))
+    torch.cuda.synchronize()
+    t = nbr.tmap.cpu().numpy()
+    BM, tiles = B * M, int(t[0])
+    off = 4 + ((BM + 3) & ~3)
+    info = t[off:off + 32 * BM].view(np.uint32)[:32 * tiles]
+    rownn, tq0 = t[off + 32 * BM:off + 64 * BM][:32 * tiles], t[4:4 + tiles]
+    mult = ((info >> 16) & 0xff).astype(np.int64)
+    rows = np.nonzero(mult)[0]                                      # the live rows, ascending
+    q = tq0[rows >> 5] + (info[rows] & 0xff).astype(np.int64)
+    pt = (q // M) * N + rownn[rows]
+    order = np.argsort(pt, kind="stable")                           # by point, then by row
+    # a cloud's places start at the first row of its first tile and are handed out in that order
+    cloud = pt[order] // N
+    first_row = 32 * np.searchsorted(tq0 // M, np.arange(B))
+    per_cloud = np.bincount(cloud, minlength=B)
+    place = first_row[cloud] + np.arange(len(rows)) - (np.cumsum(per_cloud) - per_cloud)[cloud]
+    want_pcnt = np.bincount(pt, minlength=B * N)
+    before = np.cumsum(want_pcnt) - want_pcnt                       # a list starts behind the lists of the cloud's points before it
+    of = np.arange(B * N) // N
+    want_poff = first_row[of] + before - before[of * N]
+    want_fq = np.full((B, N), -1, dtype=np.int64)
+    for b in range(B):
+        want_fq[b, picks[b].numpy()] = np.arange(M)
+    fits = M <= 1024 and 2 * N + 37 * M + 1 <= 38400
+    _LISTS[B, N, M] = dict(
+        fits=fits, rows=rows, order=order, place=place, pt=pt, mult=mult, want_pcnt=want_pcnt, want_poff=want_poff,
+        want_fq=want_fq, nbr_pcnt=nbr.pcnt_poff[:B * N].cpu().numpy(), nbr_poff=nbr.pcnt_poff[B * N:].cpu().numpy(),
+        plist=nbr.plist.cpu().numpy(), occ=nbr.geo.cpu().numpy().reshape(B * N, 4)[:, 0], fq=nbr.fq.cpu().numpy(),
+        map_pcnt=pcnt_poff[:B * N].cpu().numpy(), map_poff=pcnt_poff[B * N:2 * B * N].cpu().numpy(),
+        verdict=pcnt_poff[2 * B * N:].cpu().numpy(), rowdst=rowdst.cpu().numpy())
+    return _LISTS[B, N, M]
+
+
+@pytest.mark.parametrize("B,N,M", LIST_SHAPES[2:])
+def test_reverse_lists_on_both_sides_of_the_lds_fit_rule(dev, B, N, M):
+    """The last cloud size whose lists fit one workgroup's LDS and the first that does not: the inverse map and the row
+    map, each against numpy, bit for bit.  Which path ran shows in the row map's verdict on the (distinct) picks: 0 from
+    the one-launch kernel, 1 (not examined) from the multi-launch path."""
+    c = _lists(dev, B, N, M)
+    assert c["fits"] == (N == 18015)
+    # the inverse map: counts, list starts, ascending lists, the sum of the multiplicities, the query a point is
+    assert np.array_equal(c["nbr_pcnt"], c["want_pcnt"])
+    assert np.array_equal(c["nbr_poff"], c["want_poff"])
+    assert np.array_equal(c["plist"][c["place"]], c["rows"][c["order"]])
+    assert np.array_equal(c["occ"], np.bincount(c["pt"], weights=c["mult"][c["rows"]], minlength=B * N))
+    assert np.array_equal(c["fq"], c["want_fq"])
+    # the row map
+    assert np.array_equal(c["map_pcnt"], c["want_pcnt"])
+    assert np.array_equal(c["map_poff"], c["want_poff"])
+    assert np.array_equal(c["rowdst"][c["rows"][c["order"]]], c["place"])
+    assert c["verdict"].tolist() == [0 if c["fits"] else 1] * B
+
+
+@pytest.mark.parametrize("B,N,M", LIST_SHAPES)
+def test_inverse_map_and_row_map_are_one_builder(dev, B, N, M):
+    """apn_sa_wide_csr and apn_sa_rowmap_many over the same tile map, on either path: the same counts and list starts, and
+    rowdst is the inverse of plist -- for every point and every j < pcnt, rowdst[plist[poff + j]] == poff + j."""
+    c = _lists(dev, B, N, M)
+    assert np.array_equal(c["map_pcnt"], c["nbr_pcnt"])
+    assert np.array_equal(c["map_poff"], c["nbr_poff"])
+    cnt = c["nbr_pcnt"].astype(np.int64)
+    assert int(cnt.sum()) == len(c["rows"])
+    places = np.repeat(c["nbr_poff"], cnt) + np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt)     # poff + j
+    assert np.array_equal(c["rowdst"][c["plist"][places]], places)
 
 
 def test_skip_branch_gradient_rows_are_stored_where_the_picks_are_distinct(dev):
